@@ -22,10 +22,16 @@ round-synchronous (MTE_DOC_ROUND_SYNC: flat passes, declaration checked per
 batch); the "tree_placement" side line replays the same job with them on the
 tree pass (the reference's B+tree placement) and must give the same digests.
 
-Rank 0 prints one JSON line.  At N=1 it also times the CPU restatement
-(oracle/, kind "port") on a bounded sample of the same workload and checks the
-sampled docs' digests against the GPU's; the reference merge-tree's own CPU
-rate (measured in the build container, tools/ref_baseline.py) is attached.
+Rank 0 prints one JSON line.  A plain run does only what the headline figure
+needs: generate and upload the workload, one first run, the warmup, the timed
+steps, the result line.  --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs).  Everything else is behind --full: the accounting
+run and the roofline block, the end-to-end pass, the tree-placement,
+local-client, weak-scaling and Node host side lines, and at N=1 the CPU
+restatement (oracle/, kind "port") timed on a bounded sample of the same
+workload, with the sampled docs' digests checked against the GPU's; the
+reference merge-tree's own CPU rate (a recorded measurement,
+tools/ref_baseline.py) is attached there too.
 """
 import argparse
 import json
@@ -154,10 +160,11 @@ class NodeComm:
         self.eng.comm_destroy()
 
 
-def run_engine(stream, cap, device, steps, warmup, stats_on, barrier=lambda: None):
-    """Load + submit a stream, one accounting run (mte_stats), warmup, then
-    `steps` timed steps (reset + run) bracketed by barrier + sync.  Returns a
-    dict with the engine, elapsed seconds, kernel ms per step, stats, digest."""
+def run_engine(stream, cap, device, steps, warmup, stats_on, barrier=lambda: None, accounting=True):
+    """Load + submit a stream, one first run, one accounting run (mte_stats;
+    not with accounting=False, then stats is None), warmup, then `steps` timed
+    steps (reset + run) bracketed by barrier + sync.  Returns a dict with the
+    engine, elapsed seconds, kernel ms per step, stats, digest, statuses."""
     from fluidframework_amd import gen
     from fluidframework_amd.engine import DeviceEngine
 
@@ -180,13 +187,15 @@ def run_engine(stream, cap, device, steps, warmup, stats_on, barrier=lambda: Non
     # one accounting run (mte_stats: ops, segments scanned / written, property
     # writes, units -> the algorithmic bytes of SURVEY.md 8(d)); the timed runs
     # then go without the per-op counters (opt-in like the reference's measureOps)
-    eng.set_stats(True)
-    step()
-    eng.sync()
-    if (eng.statuses() != 0).any():
-        raise SystemExit(f"replay errors {np.unique(eng.statuses())}")
-    stats = eng.stats()
-    stats_digest = eng.digest()
+    stats = stats_digest = None
+    if accounting:
+        eng.set_stats(True)
+        step()
+        eng.sync()
+        if (eng.statuses() != 0).any():
+            raise SystemExit(f"replay errors {np.unique(eng.statuses())}")
+        stats = eng.stats()
+        stats_digest = eng.digest()
     eng.set_stats(stats_on)
     for _ in range(warmup):
         step()
@@ -208,10 +217,86 @@ def run_engine(stream, cap, device, steps, warmup, stats_on, barrier=lambda: Non
     t_elapsed = time.perf_counter() - t_start
     barrier()
     digest = eng.digest()
-    if (eng.statuses() != 0).any() or not np.array_equal(digest, stats_digest):
+    statuses = eng.statuses()
+    if (statuses != 0).any():
+        raise SystemExit(f"replay errors {np.unique(statuses)}")
+    if accounting and not np.array_equal(digest, stats_digest):
         raise SystemExit("timed runs disagree with the accounting run")
     return {"eng": eng, "elapsed": t_elapsed, "kernel_ms": kernel_ms, "stats": stats, "digest": digest,
+            "statuses": statuses,
             "first_ms": first_ms, "round_bytes": float(np.mean(round_bytes)) if round_bytes else 0.0}
+
+
+DUMP_SAMPLE_DOCS = 16      # documents whose text --dump-outputs writes
+DUMP_SAMPLE_SEED = 20240607
+DUMP_TEXT_UNITS = 1 << 16  # a sampled document longer than this is left out of the text sample
+
+
+def dump_outputs(out_dir, eng, digest, statuses, rank=0, world=1):
+    """What a caller of the timed path receives after its last step, as float64
+    .npy files in out_dir (well under 1 MB at the presets' sizes):
+      digests.npy   (docs, 8)  mte_digest: the four uint64 words of every document
+                    (units, h1, h2, sum) as (low, high) 32-bit halves, so each
+                    value is exact in float64
+      statuses.npy  (docs,)    mte_doc_status
+      text_sample_docs.npy / text_sample.npy  (S,) / (S, L)  mte_read_doc of a
+                    fixed, seeded sample of documents: their indices and their
+                    text as UTF-16 code units, padded with -1
+    A rank of an N > 1 job writes its own shard as <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    dg = np.ascontiguousarray(digest, np.uint64)
+    halves = np.stack([dg & np.uint64(0xFFFFFFFF), dg >> np.uint64(32)], axis=-1)
+    np.save(os.path.join(out_dir, f"digests{tag}.npy"), halves.reshape(len(dg), 8).astype(np.float64))
+    np.save(os.path.join(out_dir, f"statuses{tag}.npy"), np.asarray(statuses).astype(np.float64))
+    n = len(dg)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    pick = np.sort(rng.choice(n, size=min(DUMP_SAMPLE_DOCS, n), replace=False))
+    pick = [int(d) for d in pick if int(dg[d, 0]) <= DUMP_TEXT_UNITS]
+    texts = [np.frombuffer(eng.read_doc(d)["text"].encode("utf-16-le", errors="surrogatepass"), "<u2")
+             for d in pick]
+    sample = np.full((len(pick), max([len(t) for t in texts] + [1])), -1.0)
+    for i, t in enumerate(texts):
+        sample[i, :len(t)] = t
+    np.save(os.path.join(out_dir, f"text_sample_docs{tag}.npy"), np.asarray(pick, np.float64))
+    np.save(os.path.join(out_dir, f"text_sample{tag}.npy"), sample)
+
+
+def roofline_block(args, r, stats, cap, first_ms):
+    """The roofline block of the result line (--full): the accounting run's
+    algorithmic bytes over the timed steps' HIP-event kernel time."""
+    avg_kernel_ms = float(np.mean(r["kernel_ms"])) if r["kernel_ms"] else None
+    algo_bytes = stats["algo_bytes"]
+    # the chunked pass's timed runs take the round phases, whose own bytes the
+    # library counts in every run (mte_stats.round_bytes); the statistics run
+    # replays op after op, so its algo_bytes describe that pass, not the timed one
+    round_bytes = r.get("round_bytes", 0.0)
+    timed_bytes = round_bytes if cap >= 8192 and round_bytes > 0 else algo_bytes
+    achieved_gbs = timed_bytes / (avg_kernel_ms * 1e-3) / 1e9 if avg_kernel_ms else None
+    traffic, traffic_src = pmc_traffic(args.config, args.docs, args.ops)
+    return {
+        "bound": "hbm",
+        "achieved": achieved_gbs,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": (achieved_gbs / HBM_PEAK_GBS) if achieved_gbs else None,
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "traffic_frac_of_algo": (traffic / algo_bytes) if traffic else None,
+        "kernel": ("tree + pair + big + " + ("chunk" if cap >= 8192 else "stream") +
+                   " replay passes, HIP events on the engine stream"),
+        "algo_bytes_note": ("the round phases' own bytes, counted by the library in the timed runs "
+                            "(mte_stats.round_bytes: records, planes re-laid out / applied / gathered, sub-op "
+                            "lists); algo_bytes_op_after_op = SURVEY.md 8(d) with S_live replaced by the chunk "
+                            "slots + summary entries the op-after-op chunk pass scans"
+                            if cap >= 8192 and round_bytes > 0 else "SURVEY.md 8(d) B_op"),
+        "counters_in_timed_runs": bool(args.stats),
+        "kernel_ms": avg_kernel_ms,
+        "first_run_kernel_ms": first_ms,
+        "algo_bytes_per_launch": timed_bytes,
+        "algo_bytes_per_op": timed_bytes / max(1, stats["ops_applied"]),
+        "algo_bytes_op_after_op": algo_bytes if timed_bytes != algo_bytes else None,
+    }
 
 
 def main():
@@ -242,7 +327,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stats", action="store_true",
                     help="keep the per-op counters on in the timed runs (default: off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the accounting run and roofline block, the end-to-end pass, the side lines "
+                         "(tree placement, local client, weak scaling, Node host) and the CPU baselines; "
+                         "the --no-* options pick among them")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # run directly with --gpus N > 1: start the N ranks here (one process per
     # GPU, the rank variables torch.distributed.run would set), before this
@@ -297,8 +390,10 @@ def main():
     gen_s = time.time() - t0
     n_ops_rank = int(stream["batch"]["op_offsets"][-1])
     cap = gen.seg_capacity(args.config, stream["params"])
-    r = run_engine(stream, cap, local_rank, args.steps, args.warmup, args.stats, barrier)
+    r = run_engine(stream, cap, local_rank, args.steps, args.warmup, args.stats, barrier, accounting=args.full)
     eng, stats, digest = r["eng"], r["stats"], r["digest"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, digest, r["statuses"], rank, world)
     elapsed = r["elapsed"]
     first_ms = r["first_ms"]
     total_ops = n_ops_rank * world
@@ -316,34 +411,29 @@ def main():
 
     ms_per_step = elapsed * 1000.0 / args.steps
     value = total_ops / (elapsed / args.steps)
-    avg_kernel_ms = float(np.mean(r["kernel_ms"])) if r["kernel_ms"] else None
-    algo_bytes = stats["algo_bytes"]
-    # the chunked pass's timed runs take the round phases, whose own bytes the
-    # library counts in every run (mte_stats.round_bytes); the statistics run
-    # replays op after op, so its algo_bytes describe that pass, not the timed one
-    round_bytes = r.get("round_bytes", 0.0)
-    timed_bytes = round_bytes if cap >= 8192 and round_bytes > 0 else algo_bytes
-    achieved_gbs = timed_bytes / (avg_kernel_ms * 1e-3) / 1e9 if avg_kernel_ms else None
+    roofline = e2e = None
+    if args.full:
+        roofline = roofline_block(args, r, stats, cap, first_ms)
 
-    traffic, traffic_src = pmc_traffic(args.config, args.docs, args.ops)
-
-    # end-to-end: host op records -> HBM (mte_submit, PCIe),
-    # replay, per-doc digests back to the host; one untimed-by-the-contract pass
-    eng.sync()
-    t0 = time.perf_counter()
-    eng.submit(stream["batch"])
-    eng.reset()
-    eng.run()
-    e2e_digest = eng.digest()
-    e2e_s = time.perf_counter() - t0
-    if not np.array_equal(e2e_digest, digest):
-        raise SystemExit(f"rank {rank}: end-to-end pass disagrees with the timed runs")
+        # end-to-end: host op records -> HBM (mte_submit, PCIe),
+        # replay, per-doc digests back to the host; one untimed-by-the-contract pass
+        eng.sync()
+        t0 = time.perf_counter()
+        eng.submit(stream["batch"])
+        eng.reset()
+        eng.run()
+        e2e_digest = eng.digest()
+        e2e_s = time.perf_counter() - t0
+        if not np.array_equal(e2e_digest, digest):
+            raise SystemExit(f"rank {rank}: end-to-end pass disagrees with the timed runs")
+        e2e = {"ops_per_s": n_ops_rank / e2e_s, "ms": e2e_s * 1e3,
+               "includes": "mte_submit (host->HBM op upload) + reset + replay + digest read-back, rank 0"}
     del eng, r
 
     # side measurement: the same job with every legacy-calc document on the
     # tree pass (no round-synchronous declaration), digest-checked
     tree_leg = None
-    if args.placement == "round_sync" and not args.no_tree_leg and world == 1:
+    if args.full and args.placement == "round_sync" and not args.no_tree_leg and world == 1:
         ts = make_stream(args.scaling, "tree")
         rt = run_engine(ts, cap, local_rank, max(1, args.steps // 2), 1, False)
         if not np.array_equal(rt["digest"], digest):
@@ -358,12 +448,12 @@ def main():
     # side measurement: documents with a local client (the 8(f) rows: local ops
     # + acks, rollback, reconnect, delta events) on the HBM-streamed pass
     local_leg = None
-    if not args.no_local_leg and world == 1:
+    if args.full and not args.no_local_leg and world == 1:
         local_leg = local_client_leg(args.local_docs, local_rank, max(1, args.steps // 2), threads)
 
     # side measurement at N > 1: weak scaling (every rank the config's docs)
     weak_leg = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_leg:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak_leg:
         ws = make_stream("weak", args.placement)
         rw = run_engine(ws, cap, local_rank, args.steps, 1, False, barrier)
         w_el = node.max(rw["elapsed"])
@@ -378,18 +468,18 @@ def main():
         return
 
     node_e2e = None
-    if world == 1 and not args.no_node_leg and stream.get("segs") is None:
+    if args.full and world == 1 and not args.no_node_leg and stream.get("segs") is None:
         node_e2e = node_end_to_end(stream, digest, args.node_docs)
         node_e2e["sharded"] = node_sharded(stream, args.node_sharded_docs, host_threads())
 
     cpu = None
     parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         if stream.get("segs") is not None:
             cpu, parity = cpu_baseline(stream, digest, args.cpu_seconds, tree="chunked")
         else:
             cpu, parity = cpu_baseline(stream, digest, args.cpu_seconds)
-    ref_cpu = reference_cpu_baseline(args.config)
+    ref_cpu = reference_cpu_baseline(args.config) if args.full else None
 
     out = {
         "metric": METRIC,
@@ -416,31 +506,10 @@ def main():
             "parallelism": f"doc-sharded x{world} by expected work (LPT), no data-path collective",
             "collective": node.kind if node is not None else None,
         },
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved_gbs,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (achieved_gbs / HBM_PEAK_GBS) if achieved_gbs else None,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "traffic_frac_of_algo": (traffic / algo_bytes) if traffic else None,
-            "kernel": ("tree + pair + big + " + ("chunk" if cap >= 8192 else "stream") +
-                       " replay passes, HIP events on the engine stream"),
-            "algo_bytes_note": ("the round phases' own bytes, counted by the library in the timed runs "
-                                "(mte_stats.round_bytes: records, planes re-laid out / applied / gathered, sub-op "
-                                "lists); algo_bytes_op_after_op = SURVEY.md 8(d) with S_live replaced by the chunk "
-                                "slots + summary entries the op-after-op chunk pass scans"
-                                if cap >= 8192 and round_bytes > 0 else "SURVEY.md 8(d) B_op"),
-            "counters_in_timed_runs": bool(args.stats),
-            "kernel_ms": avg_kernel_ms,
-            "first_run_kernel_ms": first_ms,
-            "algo_bytes_per_launch": timed_bytes,
-            "algo_bytes_per_op": timed_bytes / max(1, stats["ops_applied"]),
-            "algo_bytes_op_after_op": algo_bytes if timed_bytes != algo_bytes else None,
-        },
-        "end_to_end": {"ops_per_s": n_ops_rank / e2e_s, "ms": e2e_s * 1e3,
-                       "includes": "mte_submit (host->HBM op upload) + reset + replay + digest read-back, rank 0"},
+        # the side blocks below are measured with --full only (None in a plain run)
+        "full": bool(args.full),
+        "roofline": roofline,
+        "end_to_end": e2e,
         "end_to_end_node": node_e2e,
         "tree_placement": tree_leg,
         "local_client": local_leg,

@@ -3,13 +3,13 @@
 
 Usage: pmc_traffic.py FETCH_DIR WRITE_DIR OUT_JSON [--workload config3] [--sum-last-run]
 
-Both passes run `bench.py --steps 1 --warmup 0 --no-cpu-baseline`, so the
-replay kernels are dispatched twice (the accounting run with counters on, then
-the timed run without): the LAST dispatch of each kernel is the timed one.
+Both passes run a plain `bench.py --steps 1 --warmup 0` (no --full), so the
+replay kernels are dispatched twice (the first run of the context, then the
+timed run): the LAST dispatch of each kernel is the timed one.
 With --sum-last-run (a launch that dispatches kernels many times: the chunked
 pass's round phases, config 5) every path kernel dispatched after the last
-begin_batch_kernel (the timed launch's first kernel) is summed instead; run
-bench.py without its side legs so the timed launch is the last one.
+begin_batch_kernel (the timed launch's first kernel) is summed instead; the
+plain run has no side legs, so the timed launch is the last one.
 The counters are in KiB.  Corrections per MI355X_MICROARCH.md (HBM/rocprofv3):
 FETCH_SIZE counts half the bytes of wide coalesced reads on gfx950, so it is
 doubled; WRITE_SIZE is taken as is.  The op records are read by scalar loads
