@@ -531,6 +531,7 @@ struct mte_ctx {
   hipStream_t tree_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool ran = false, submitted = false;
+  bool rounds_carried = false;  // a round-phase run laid documents out in the arena since the load / reset
   bool stats_on = true;
   std::string err;
 
@@ -826,6 +827,7 @@ void free_docs(mte_ctx* c) {
   c->d_pairs = nullptr;
   c->n_pairs = 0;
   c->n_docs = 0;
+  c->rounds_carried = false;
 }
 
 int launch_reset(mte_ctx* c) {
@@ -846,6 +848,7 @@ int launch_reset(mte_ctx* c) {
     HIPCHK(c, hipGetLastError());
   }
   c->ran = false;
+  c->rounds_carried = false;
   return MTE_OK;
 }
 
@@ -884,6 +887,7 @@ int round_phase_loop(mte_ctx* c, const ReplayArgs& a, size_t lds) {
       HIPCHK(c, hipMemsetAsync(rd.rflag, 0, 4 * (uint64_t)c->n_docs, c->stream));
       HIPCHK(c, (launch_round_run<K>(a, ch, rd, c->n_docs, c->stream)));
       carried = true;
+      c->rounds_carried = true;
     } else if (carried) {  // the carried documents' runs are not rounds: back to the flat planes
       HIPCHK(c, (launch_round_gather<K>(a, ch, rd, 0, c->stream)));
     }
@@ -2160,10 +2164,19 @@ int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: a segment removed by a short id >= 32 (mte_seg.removers)", doc);
   uint64_t nt = 0;
   uint64_t m = 0;  // segments out (a tree pass placeholder is none, a merged leaf one)
+  // The round phases carry a document's chunks from run to run without a
+  // re-layout (mte_round.h), so after them (rounds_carried) a flat document's
+  // planes may still hold tombstones at or below minSeq, which every other
+  // flat pass drops when minSeq moves (as the
+  // reference's scour does in its own time, mergeTree.ts:681-747).  No later
+  // op sees them and a summary leaves them out (snapshotV1.ts:195-199): the
+  // list is the canonical one, without them.
+  const bool lazy_zamboni = c->rounds_carried && !c->h_legacy[doc];
   for (uint32_t i = 0; i < n; i++) {
     const int32_t len = (int32_t)pl[i], rseq = (int32_t)pl[2 * (size_t)n + i];
     const uint32_t meta = pl[4 * (size_t)n + i], kind = meta >> 8;
     if (tw[i] & kTEmpty) continue;
+    if (lazy_zamboni && rseq != kNone && rseq <= h.min_seq) continue;
     if ((tw[i] & kTCont) && m > 0) {
       if (m - 1 < v->seg_cap && v->segs) v->segs[m - 1].len += (uint32_t)len;
       const uint32_t toff = pl[5 * (size_t)n + i];

@@ -602,6 +602,13 @@ __device__ __forceinline__ int doc_step(Regs<E, K>& R, DocRun& D, uint32_t (&st)
           for (int kk = 0; kk < kRegPlanes<K>; kk++)
 #pragma unroll
             for (int jj = 0; jj < E; jj++) R.pr[kk][jj] = in[jj] ? 0u : R.pr[kk][jj];
+          if constexpr (K == kPack4) {
+            // the side key's value of a marker is in its toff register (load_regs)
+            if (a.side_key < 4u) {
+#pragma unroll
+              for (int jj = 0; jj < E; jj++) R.toff[jj] = (in[jj] && (R.meta[jj] >> 8)) ? 0u : R.toff[jj];
+            }
+          }
         }
         apply_props<E, K>(R.pr, in, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
         MTE_STAT(st[kStPwrites] += cnt * (uint32_t)q2[3];)

@@ -395,6 +395,13 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
           for (int kk = 0; kk < kRegPlanes<K>; kk++)
 #pragma unroll
             for (int j = 0; j < E; j++) R.pr[kk][j] = in[j] ? 0u : R.pr[kk][j];
+          if constexpr (K == kPack4) {
+            // the side key's value of a marker is in its toff register (put_new_v)
+            if (a.side_key < 4u) {
+#pragma unroll
+              for (int j = 0; j < E; j++) R.toff[j] = (in[j] && (R.meta[j] >> 8)) ? 0u : R.toff[j];
+            }
+          }
         }
         apply_props<E, K>(R.pr, in, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
         MTE_STAT(st[kStPwrites] += cnt * (uint32_t)q2[3];)

@@ -6,6 +6,7 @@ import pytest
 
 from fixtures_util import replay_fixtures
 from scenarios import PROPS_AT, SCENARIOS, expected_of, props_at, run_scenario
+from flat_checks import assert_stopped_like_spec, resident_docs
 
 from fluidframework_amd import gen
 from fluidframework_amd.abi import MTE_E_CAPACITY
@@ -138,6 +139,7 @@ def test_gpu_capacity_error_is_reported():
     assert o.stats()["max_segs"] > 1022
     st = d.statuses()
     assert (st == MTE_E_CAPACITY).all()
+    assert_stopped_like_spec(s, d, 1024, streamed=False)  # stops in the last register tier
 
 
 def replay_both_cap(stream, cap, threads=8):
@@ -208,6 +210,7 @@ def test_gpu_stream_pass_capacity_error():
     o, d = replay_both_cap(s, 1536)
     assert o.stats()["max_segs"] > 1534
     assert (d.statuses() == MTE_E_CAPACITY).all()
+    assert_stopped_like_spec(s, d, 1536, streamed=True)
 
 
 @pytest.mark.gpu
@@ -249,9 +252,11 @@ def test_gpu_submit_rejects_bad_record():
 
 @pytest.mark.gpu
 def test_gpu_paired_pass1_matches_oracle():
-    # > CUs x 4 x 5 docs: pass 1 runs two documents per wave (alternating
-    # bursts); smaller batches run one per wave
-    s = gen.generate(3, n_docs=6000, ops_per_doc=300)
+    # > CUs x 4 x 5 flat docs (MTE_PAIR_WAVES, mte_replay.h; `resident` in
+    # mte_load_docs): pass 1 runs two documents per wave (alternating bursts);
+    # smaller batches run one per wave.  length_mode 2: every document is flat
+    # (of a default stream half are legacy and replay on the tree pass)
+    s = gen.generate(3, n_docs=resident_docs() + 1, ops_per_doc=300, length_mode=2)
     o, d = replay_both(s, threads=16)
     assert (o.statuses() == 0).all()
     assert_same(o, d, sample_docs=24)
