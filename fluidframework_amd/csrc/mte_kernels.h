@@ -230,20 +230,25 @@ struct Regs {
 
 // Perspective length of every slot (mergeTree.ts:1003-1026 new calc,
 // 1028-1054 legacy calc); -1 = undefined.  Written as selects on compare
-// results so no per-slot mask arithmetic lands on the scalar unit.
+// results so no per-slot mask arithmetic lands on the scalar unit.  PIN (the
+// pass-1 step): the inner select of each nest passes through an empty asm, or
+// the nest is folded into one select on the AND of its two lane masks (a
+// scalar instruction per slot).
 //   new:    rseq <= m ? UNDEF : (rseq <= r || c in rcli) ? 0 : seen ? len : 0
 //   legacy: rseq <= r ? UNDEF : seen ? (c in rcli ? 0 : len) : removed ? UNDEF : 0
 // with seen = seq <= r || cli == c.  Padding (rseq INT32_MIN) is UNDEF in both.
-template <int E, int K>
+template <int E, int K, bool PIN = false>
 __device__ __forceinline__ void leaf_lengths(const Regs<E, K>& R, int32_t r, uint32_t cm1, int c, int32_t m,
                                              bool newcalc, int32_t (&L)[E]) {
   if (newcalc) {
 #pragma unroll
     for (int j = 0; j < E; j++) {
       const int32_t seqe = ((R.meta[j] & 0xffu) == cm1) ? INT32_MIN : R.seq[j];
-      const int32_t vis = (seqe <= r) ? R.len[j] : 0;
+      int32_t vis = (seqe <= r) ? R.len[j] : 0;
+      if constexpr (PIN) asm("" : "+v"(vis));
       const int32_t rse = ((R.rmask[j] >> c) & 1u) ? INT32_MIN : R.rseq[j];
-      const int32_t v2 = (rse <= r) ? 0 : vis;
+      int32_t v2 = (rse <= r) ? 0 : vis;
+      if constexpr (PIN) asm("" : "+v"(v2));
       L[j] = (R.rseq[j] <= m) ? -1 : v2;
     }
   } else {
@@ -252,7 +257,8 @@ __device__ __forceinline__ void leaf_lengths(const Regs<E, K>& R, int32_t r, uin
       const int32_t seqe = ((R.meta[j] & 0xffu) == cm1) ? INT32_MIN : R.seq[j];
       const int32_t lenc = ((R.rmask[j] >> c) & 1u) ? 0 : R.len[j];
       const int32_t unseen = (R.rseq[j] != kNone) ? -1 : 0;
-      const int32_t sel = (seqe <= r) ? lenc : unseen;
+      int32_t sel = (seqe <= r) ? lenc : unseen;
+      if constexpr (PIN) asm("" : "+v"(sel));
       L[j] = (R.rseq[j] <= r) ? -1 : sel;
     }
   }

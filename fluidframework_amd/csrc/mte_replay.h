@@ -99,9 +99,10 @@ __device__ __forceinline__ s8v sload_props(const ReplayArgs& a, uint32_t psi) { 
 // vmcnt, so the LDS traffic of an op (shift permutes, zamboni) never waits for
 // the next record as it does for a scalar load in flight (SMEM and LDS share
 // lgkmcnt, and SMEM returns out of order, so any LDS wait becomes lgkmcnt(0)).
+// Every lane loads (lanes >= 8 repeat lanes 0-7, the same cache line), so the
+// load needs no change of the exec mask around it; only lanes 0-7 are read.
 __device__ __forceinline__ uint32_t vload_rec8(const uint4* rec) {
-  const int l = __lane_id();
-  return l < 8 ? reinterpret_cast<const uint32_t*>(rec)[l] : 0u;
+  return reinterpret_cast<const uint32_t*>(rec)[__lane_id() & 7];
 }
 #if MTE_VREC
 typedef uint32_t RecV;  // the prefetched record of the pass-1 tiers (doc_step_v)
@@ -750,13 +751,23 @@ template <int E, int K, bool S>
 __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32_t* zlds, int emin, uint32_t limit) {
   Regs<E, K> R;
   uint32_t st[kNumStats] = {};
+  if constexpr (E <= MTE_STEPV_EMAX) {
+    // pass 1 reads `a` in place (args_in_place).  What every step reads of it
+    // (cps, side_key, cap) the compiler hoists out of the op loop itself;
+    // text_base is first read under the step's insert branch and would be
+    // loaded there, on every insert, so it is read once here
+    const uint32_t text_base = a.text_base;
+    asm volatile("" ::"s"(text_base));
+  }
   load_regs<E, K>(R, D, a);
   const uint32_t kend = D.k1 - D.k > limit ? D.k + limit : D.k1;
   s8v cur;
   RecV vcur;
+  [[maybe_unused]] const uint32_t* vrec = nullptr;  // this lane's dword of the record in vcur
   if constexpr (E <= MTE_STEPV_EMAX) {
 #if MTE_VREC
-    vcur = vload_rec8(D.recp + 2 * D.k);
+    vrec = reinterpret_cast<const uint32_t*>(D.recp + 2 * D.k) + (lane_id() & 7);
+    vcur = *vrec;
 #else
     vcur = sload8(D.recp + 2 * D.k);
 #endif
@@ -773,7 +784,7 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   for (;;) {
     if (!per_burst && (D.k & (kTouchSpan / 2 - 1)) == 0) touch_records(D, D.k + kTouchSpan / 2, pending, sink);
     int rc;
-    if constexpr (E <= MTE_STEPV_EMAX) rc = doc_step_v<E, K, S>(R, D, st, vcur, a, zlds, emin);
+    if constexpr (E <= MTE_STEPV_EMAX) rc = doc_step_v<E, K, S>(R, D, st, vcur, vrec, a, zlds, emin);
     else rc = doc_step<E, K, S>(R, D, st, cur, a, zlds, emin);
     if (rc != 0) {
       if (rc < 0) {
@@ -968,12 +979,28 @@ __device__ __forceinline__ void fair_prio(uint32_t left, uint32_t total) {
   }
 }
 
+// The kernel's ReplayArgs, read in place from the kernel argument segment (they
+// are the kernel's first argument).  Taken by value, every field is loaded at
+// the kernel's entry and then lives in an SGPR for the whole kernel, or in a
+// spill lane, though the op loop reads four of them: with the scalar registers
+// full, the loop's own values get spilled around them.  Through this reference
+// each field is a scalar load where it is used (the pointer passes through an
+// empty asm so the loads stay there), and burst_run reads the op loop's fields
+// once, ahead of the loop.
+__device__ __forceinline__ const ReplayArgs& args_in_place() {
+  typedef const __attribute__((address_space(4))) ReplayArgs* kargp;
+  uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr());
+  asm("" : "+s"(p));
+  return *(const ReplayArgs*)(kargp)p;
+}
+
 // pass 1: `a.group` documents per wavefront (1 when the batch fits the chip
 // at one per wave), replayed in turn one burst each, so a 10k-document batch is
 // resident on the chip at once with the register budget of one document
 // (E <= 4); W = waves per SIMD the register budget is sized for
 template <int K, bool S, int WPB, int W>
-__global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayArgs a) {
+__global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayArgs) {
+  const ReplayArgs& a = args_in_place();
   __shared__ uint32_t zlds_all[WPB][kWave * 4];
   __shared__ DocHdr hl_all[WPB][kGroupMax];
   const int w = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));

@@ -22,32 +22,55 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// A[j] = some flagged slot lies before slot j (in this lane or a lower one)
-template <int E>
-__device__ __forceinline__ void after_flag(const bool (&F)[E], bool (&A)[E]) {
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < E; j++) any = any || F[j];
-  bool run = lanes_below(__ballot(any)) != 0;
-#pragma unroll
-  for (int j = 0; j < E; j++) {
-    A[j] = run;
-    run = run || F[j];
-  }
+// ---- per-slot flags ----------------------------------------------------------
+// A per-slot flag is one bit of an integer held per lane: bit j of the word is
+// the flag of slot j.  Flags are combined with integer VALU ops; a lane mask
+// (v_cmp into an SGPR pair) is made only where a select consumes one.  As
+// bools every && / || / ! between flags is a 64-bit scalar instruction per
+// slot, on the one scalar unit the CU's four SIMDs share.  The words pass
+// through an empty asm (as in pick(), mte_kernels.h): without it the compiler
+// folds the integer logic back into lane-mask logic.
+__device__ __forceinline__ uint32_t vpin(uint32_t x) {
+  asm("" : "+v"(x));
+  return x;
 }
 
-// F1[j] / F2[j] = the flag of the slot 1 / 2 positions before slot j
 template <int E>
-__device__ __forceinline__ void prev_flags(const bool (&F)[E], bool (&F1)[E], bool (&F2)[E]) {
-  const bool p1 = lane_prev(F[E - 1] ? 1 : 0) != 0;
-  bool p2;
-  if constexpr (E >= 2) p2 = lane_prev(F[E >= 2 ? E - 2 : 0] ? 1 : 0) != 0;
-  else p2 = lane_prev(p1 ? 1 : 0) != 0;
+constexpr uint32_t kAllSlots = (1u << E) - 1u;
+
+// the word with bit j set where c holds
+__device__ __forceinline__ uint32_t fbit(bool c, int j) { return vpin(c ? (1u << j) : 0u); }
+// flag of slot j (w pinned)
+__device__ __forceinline__ bool fget(uint32_t w, int j) { return ((w >> j) & 1u) != 0; }
+
+template <int E>
+__device__ __forceinline__ void funpack(uint32_t w, bool (&b)[E]) {
 #pragma unroll
-  for (int j = 0; j < E; j++) {
-    F1[j] = j >= 1 ? F[j >= 1 ? j - 1 : 0] : p1;
-    F2[j] = j >= 2 ? F[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2);
+  for (int j = 0; j < E; j++) b[j] = fget(w, j);
+}
+
+// bit j = some flagged slot lies before slot j (in this lane or a lower one)
+template <int E>
+__device__ __forceinline__ uint32_t after_flag(uint32_t F) {
+  const uint32_t below = lanes_below(__ballot(F != 0));
+  uint32_t pe = 0;  // flags of this lane's earlier slots, or-ed
+  if constexpr (E > 1) {
+    pe = F << 1;
+#pragma unroll
+    for (int sh = 1; sh < E - 1; sh <<= 1) pe |= pe << sh;
+    pe &= kAllSlots<E>;
   }
+  return vpin(pe | (below ? kAllSlots<E> : 0u));
+}
+
+// bit j of F1 / F2 = the flag of the slot 1 / 2 positions before slot j
+template <int E>
+__device__ __forceinline__ void prev_flags(uint32_t F, uint32_t& F1, uint32_t& F2) {
+  // the previous lane's flags below this lane's (lane 0 gets 0)
+  const uint32_t cat = (F << E) | (uint32_t)lane_prev((int32_t)F);
+  F1 = vpin((cat >> (E - 1)) & kAllSlots<E>);
+  if constexpr (E >= 2) F2 = vpin((cat >> (E >= 2 ? E - 2 : 0)) & kAllSlots<E>);
+  else F2 = vpin((uint32_t)lane_prev((int32_t)F1));
 }
 
 template <typename T>
@@ -87,12 +110,17 @@ __device__ __forceinline__ void shift1_dpp(T (&F)[1], bool g1, bool g2) {
   F[0] = g2 ? (T)p2 : (g1 ? (T)p1 : F[0]);
 }
 
-// new[i] = old[i - d(i)], d = g1 + g2 (g2 implies g1), for every plane and
-// the NX extra per-slot values X.  E == 1: one ds_bpermute per plane.  E > 1:
+// new[i] = old[i - d(i)], d = g1 + g2 (g2 implies g1; flag words), for every
+// plane and the NX extra per-slot values X.  E == 1: one ds_bpermute per plane.  E > 1:
 // the two cross-lane moves of every plane first (DPP), then the selects.
 template <int E, int K, int NX>
-__device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX : 1][E], const bool (&g1)[E],
-                                        const bool (&g2)[E]) {
+__device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX : 1][E], uint32_t g1w,
+                                        uint32_t g2w) {
+  bool g1[E], g2[E];
+  if constexpr (E > 1 || MTE_E1_DPP) {
+    funpack<E>(g1w, g1);
+    funpack<E>(g2w, g2);
+  }
   if constexpr (E == 1 && MTE_E1_DPP) {
     // new = d == 2 ? old[l-2] : d == 1 ? old[l-1] : old, two wave_shr:1 moves per plane
     shift1_dpp(R.len, g1[0], g2[0]);
@@ -106,7 +134,7 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
 #pragma unroll
     for (int x = 0; x < NX; x++) shift1_dpp(X[x], g1[0], g2[0]);
   } else if constexpr (E == 1) {
-    const int addr = (lane_id() - (g1[0] ? 1 : 0) - (g2[0] ? 1 : 0)) << 2;
+    const int addr = (lane_id() - (int)g1w - (int)g2w) << 2;
     perm_plane<E>(R.len, addr);
     perm_plane<E>(R.seq, addr);
     perm_plane<E>(R.rseq, addr);
@@ -159,10 +187,10 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
   }
 }
 
-// the inserted segment at the slots with `at` (mergeTree.ts:1599-1611,
+// the inserted segment at the slots flagged in `atw` (mergeTree.ts:1599-1611,
 // textSegment.ts:40-48, mergeTreeNodes.ts:602-609)
 template <int E, int K, bool S>
-__device__ __forceinline__ void put_new_v(Regs<E, K>& R, const bool (&at)[E], const s8v& op, uint32_t c,
+__device__ __forceinline__ void put_new_v(Regs<E, K>& R, uint32_t atw, const s8v& op, uint32_t c,
                                           uint32_t flags, const ReplayArgs& a, uint32_t (&st)[kNumStats],
                                           const s8v* pq) {
   const int32_t s = op[0], pos2 = op[5];
@@ -196,6 +224,8 @@ __device__ __forceinline__ void put_new_v(Regs<E, K>& R, const bool (&at)[E], co
     }
   }
   MTE_STAT(if (!marker) st[kStUnits] += (uint32_t)pos2;)
+  bool at[E];
+  funpack<E>(atw, at);
 #pragma unroll
   for (int j = 0; j < E; j++) {
     R.len[j] = at[j] ? nlen : R.len[j];
@@ -229,7 +259,7 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
   const int32_t pos1 = op[4] - (CH ? off : 0);
   const int32_t pos2 = (CH && type != MTE_OP_INSERT) ? op[5] - off : op[5];
   int32_t L[E], P[E];
-  leaf_lengths<E, K>(R, r, c + 1, (int)c, m, newcalc, L);
+  leaf_lengths<E, K, true>(R, r, c + 1, (int)c, m, newcalc, L);
   const int32_t total = prefix<E>(L, P);
   if constexpr (CH) {
     tot = total;
@@ -245,116 +275,112 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
     const bool marker = (flags & MTE_F_MARKER) != 0;
     const int32_t nlen = marker ? 1 : pos2;
     int32_t X[1][E];  // split offset, meaningful at the split leaf
-    bool sp[E], any = false;
+    uint32_t sp = 0;
 #pragma unroll
     for (int j = 0; j < E; j++) {
       X[0][j] = pos1 - P[j];
-      sp[j] = ((uint32_t)X[0][j] - 1u) < slim[j];
-      any = any || sp[j];
+      sp |= fbit(((uint32_t)X[0][j] - 1u) < slim[j], j);
     }
-    bool at[E];
-#pragma unroll
-    for (int j = 0; j < E; j++) at[j] = false;
-    if (__ballot(any)) {
+    sp = vpin(sp);
+    uint32_t at = 0;
+    if (__ballot(sp != 0)) {
       // ensureIntervalBoundary: [head][new][tail], the tail a copy of the leaf
-      bool A[E], nb[E], nb2[E], g2[E];
-      after_flag<E>(sp, A);
+      const uint32_t ins = uni(nlen > 0 ? ~0u : 0u);  // wave-uniform, an integer operand of the flag logic
+      const uint32_t A = after_flag<E>(sp);
+      uint32_t nb, nb2;
       prev_flags<E>(sp, nb, nb2);
-#pragma unroll
-      for (int j = 0; j < E; j++) g2[j] = nlen > 0 && A[j] && !nb[j];
-      bool own[E];
-#pragma unroll
-      for (int j = 0; j < E; j++) own[j] = sp[j];
+      const uint32_t g2 = vpin(A & ~nb & ins);
       shift_v<E, K, 1>(R, X, A, g2);
+      const uint32_t tail = vpin((nb2 & ins) | (nb & ~ins));
 #pragma unroll
       for (int j = 0; j < E; j++) {
-        const bool tail = nlen > 0 ? nb2[j] : nb[j];
-        R.len[j] = own[j] ? X[0][j] : (tail ? R.len[j] - X[0][j] : R.len[j]);
-        R.toff[j] = tail ? R.toff[j] + (uint32_t)X[0][j] : R.toff[j];
-        at[j] = nlen > 0 && nb[j];
+        const bool own = fget(sp, j), tl = fget(tail, j);
+        R.len[j] = own ? X[0][j] : (tl ? R.len[j] - X[0][j] : R.len[j]);
+        R.toff[j] = tl ? R.toff[j] + (uint32_t)X[0][j] : R.toff[j];
       }
+      at = nb & ins;
       n += nlen > 0 ? 2 : 1;
       MTE_STAT(st[kStWritten] += nlen > 0 ? 3u : 2u;)
     } else if (nlen > 0) {
       // insertingWalk: before the first defined leaf with P >= pos
-      bool cand[E], anyc = false;
+      uint32_t cand = 0;
 #pragma unroll
       for (int j = 0; j < E; j++) {
-        cand[j] = L[j] >= 0 && P[j] >= pos1;
-        anyc = anyc || cand[j];
+        const uint32_t def = fbit(L[j] >= 0, j);
+        cand |= vpin(P[j] >= pos1 ? def : 0u);
       }
-      if (__ballot(anyc)) {
-        bool A[E], g1[E], g2[E];
-        after_flag<E>(cand, A);
-#pragma unroll
-        for (int j = 0; j < E; j++) {
-          at[j] = cand[j] && !A[j];
-          g1[j] = A[j] || cand[j];
-          g2[j] = false;
-        }
+      cand = vpin(cand);
+      if (__ballot(cand != 0)) {
+        const uint32_t A = after_flag<E>(cand);
+        at = cand & ~A;
         int32_t none[1][E];
-        shift_v<E, K, 0>(R, none, g1, g2);
+        shift_v<E, K, 0>(R, none, vpin(A | cand), 0u);
       } else {
         if (CH && !last) return kNextChunk;  // the slot is in a later chunk
         if (pos1 > total) return MTE_E_INSERT_FAILED;  // mergeTree.ts:1666-1672
-#pragma unroll
-        for (int j = 0; j < E; j++) at[j] = base + j == n;  // append: the slot is padding
+        const uint32_t d = (uint32_t)(n - base);  // append: the slot is padding
+        at = d < (uint32_t)E ? 1u << (d & 31u) : 0u;
       }
       n += 1;
       MTE_STAT(st[kStWritten] += 1;)
     }
+    at = vpin(at);
     if (nlen > 0) put_new_v<E, K, S>(R, at, op, c, flags, a, st, pq);
     if constexpr (CH) dlen = nlen > 0 ? nlen : 0;
   } else {
     // markRangeRemoved / annotateRange: ensureIntervalBoundary at both ends
     // (ordered by position), then mark start <= P < end
     const int32_t b1 = pos1 < pos2 ? pos1 : pos2, b2 = pos1 < pos2 ? pos2 : pos1;
-    bool s1[E], s2[E], any1 = false, any2 = false;
+    uint32_t s1 = 0, s2 = 0;
 #pragma unroll
     for (int j = 0; j < E; j++) {
-      s1[j] = ((uint32_t)(b1 - P[j]) - 1u) < slim[j];
-      s2[j] = b2 != b1 && ((uint32_t)(b2 - P[j]) - 1u) < slim[j];
-      any1 = any1 || s1[j];
-      any2 = any2 || s2[j];
+      s1 |= fbit(((uint32_t)(b1 - P[j]) - 1u) < slim[j], j);
+      s2 |= fbit(((uint32_t)(b2 - P[j]) - 1u) < slim[j], j);
     }
-    uint64_t m1 = __ballot(any1), m2 = __ballot(any2);
+    s1 = vpin(s1);
+    s2 = vpin(b2 != b1 ? s2 : 0u);
+    uint64_t m1 = __ballot(s1 != 0), m2 = __ballot(s2 != 0);
     int32_t bA = b1;
     if (!m1) {  // only the end splits: it acts as the first split
-#pragma unroll
-      for (int j = 0; j < E; j++) {
-        s1[j] = s2[j];
-        s2[j] = false;
-      }
+      s1 = s2;
+      s2 = 0;
       m1 = m2;
       m2 = 0;
       bA = b2;
     }
     if (m1) {
-      bool A[E], AB[E], nbB[E], nbB2[E], B[E];
-      after_flag<E>(s1, A);
-      after_flag<E>(s2, AB);
-      prev_flags<E>(s2, nbB, nbB2);
+      const uint32_t A = after_flag<E>(s1);
+      uint32_t B = 0;  // after the second split leaf's head (no second split: no slot)
+      if (m2) {
+        uint32_t nbB, nbB2;
+        prev_flags<E>(s2, nbB, nbB2);
+        B = vpin(after_flag<E>(s2) & ~nbB);
+      }
       int32_t X[3][E];  // L, P and the split flags travel with the slot
 #pragma unroll
       for (int j = 0; j < E; j++) {
-        B[j] = m2 != 0 && AB[j] && !nbB[j];
         X[0][j] = L[j];
         X[1][j] = P[j];
-        X[2][j] = (s1[j] ? 1 : 0) | (s2[j] ? 2 : 0);
+        X[2][j] = (int32_t)(((s1 >> j) & 1u) | (((s2 >> j) & 1u) << 1));
       }
       shift_v<E, K, 3>(R, X, A, B);
 #pragma unroll
       for (int j = 0; j < E; j++) {
-        // which piece of its source leaf slot j now holds
-        const int d = (A[j] ? 1 : 0) + (B[j] ? 1 : 0);
-        const bool h1 = (X[2][j] & 1) != 0, h2 = (X[2][j] & 2) != 0;
+        // which piece of its source leaf slot j now holds: piece kp of 1 + h1 +
+        // h2, cut at cutA and (both ends in the leaf) at oB; every select below
+        // is on one integer compare
+        const int32_t hh = (int32_t)vpin((uint32_t)X[2][j]);
+        const int32_t h1 = hh & 1, h2 = hh >> 1;
+        const int32_t d = (int32_t)(((A >> j) & 1u) + ((B >> j) & 1u));
         const int32_t oA = bA - X[1][j], oB = b2 - X[1][j];
-        const int kp = h1 ? d : d - 1;
+        const int32_t kp = hh ? d - 1 + h1 : 0;  // an unsplit leaf is its own only piece
         const int32_t cutA = h1 ? oA : oB;
-        const int32_t st0 = (h1 || h2) ? (kp == 0 ? 0 : (kp == 1 ? cutA : oB)) : 0;
-        const int32_t en = (h1 || h2) ? (kp == 0 ? cutA : ((kp == 1 && h1 && h2) ? oB : R.len[j])) : R.len[j];
+        const int32_t mid = kp == 1 ? cutA : oB;
+        const int32_t st0 = kp < 1 ? 0 : mid;
+        const int32_t cut = kp == 0 ? cutA : oB;
+        const int32_t en = kp >= h1 + h2 ? R.len[j] : cut;
         const int32_t nl = en - st0;
-        L[j] = (h1 || h2) ? nl : X[0][j];
+        L[j] = hh ? nl : X[0][j];
         P[j] = X[1][j] + st0;
         R.len[j] = nl;
         R.toff[j] += (uint32_t)st0;
@@ -363,13 +389,24 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
       MTE_STAT(st[kStWritten] += m2 ? 4u : 2u;)
     }
     if (pos2 != pos1) {
-      // nodeMap (mergeTree.ts:2274-2330): no visible leaf straddles a boundary
-      bool in[E];
-      uint32_t cnt = 0;
+      // nodeMap (mergeTree.ts:2274-2330): no visible leaf straddles a boundary.
+      // pos1 <= P < pos2 as one unsigned compare (an empty range when pos2 < pos1)
+      const uint32_t span = pos2 > pos1 ? (uint32_t)pos2 - (uint32_t)pos1 : 0u;
+      uint32_t inw = 0;
 #pragma unroll
       for (int j = 0; j < E; j++) {
-        in[j] = L[j] > 0 && P[j] >= pos1 && P[j] < pos2;
-        cnt += (uint32_t)__popcll(__ballot(in[j]));
+        const uint32_t vis = fbit(L[j] > 0, j);
+        inw |= vpin(((uint32_t)P[j] - (uint32_t)pos1) < span ? vis : 0u);
+      }
+      inw = vpin(inw);
+      bool in[E];
+      funpack<E>(inw, in);
+      uint32_t cnt = 0;  // marked slots (S), else only whether there is one
+      if constexpr (S) {
+#pragma unroll
+        for (int j = 0; j < E; j++) cnt += (uint32_t)__popcll(__ballot(in[j]));
+      } else {
+        cnt = __ballot(inw != 0) ? 1u : 0u;
       }
       MTE_STAT(st[kStWritten] += cnt;)
       if (type == MTE_OP_REMOVE) {
@@ -377,7 +414,8 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
         const uint32_t bit = 1u << c;
 #pragma unroll
         for (int j = 0; j < E; j++) {
-          R.rseq[j] = (in[j] && R.rseq[j] == kNone) ? s : R.rseq[j];
+          const int32_t first = (int32_t)vpin((uint32_t)(R.rseq[j] == kNone ? s : R.rseq[j]));
+          R.rseq[j] = in[j] ? first : R.rseq[j];
           R.rmask[j] = in[j] ? (R.rmask[j] | bit) : R.rmask[j];
         }
         if constexpr (CH) {  // the remover's own view loses the marked units
@@ -399,7 +437,10 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
             // the side key's value of a marker is in its toff register (put_new_v)
             if (a.side_key < 4u) {
 #pragma unroll
-              for (int j = 0; j < E; j++) R.toff[j] = (in[j] && (R.meta[j] >> 8)) ? 0u : R.toff[j];
+              for (int j = 0; j < E; j++) {
+                const uint32_t cleared = vpin((R.meta[j] >> 8) ? 0u : R.toff[j]);
+                R.toff[j] = in[j] ? cleared : R.toff[j];
+              }
             }
           }
         }
@@ -413,7 +454,7 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
 
 template <int E, int K, bool S>
 __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&st)[kNumStats], RecV& cur,
-                                          const ReplayArgs& a, uint32_t* zlds, int emin) {
+                                          const uint32_t*& vrec, const ReplayArgs& a, uint32_t* zlds, int emin) {
   const int l = lane_id();
   const int base = l * E;
   const int lim = kWave * E < (int)a.cap ? kWave * E : (int)a.cap;
@@ -423,13 +464,16 @@ __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&s
   }
 
   // ---- op record (prefetched into `cur`; see doc_step) ----------------------
-  const uint4* rec = D.recp + 2 * D.k;
 #if MTE_VREC
   s8v op;
 #pragma unroll
   for (int i = 0; i < 8; i++) op[i] = (int32_t)rdlane(cur, i);
-  cur = vload_rec8(rec + 2);  // the next record (zeroed pad after the last)
+  // the next record (zeroed pad after the last); vrec is this lane's running
+  // pointer into the records (vload_rec8), so no address is formed per op
+  vrec += 8;
+  cur = *vrec;
 #else
+  const uint4* rec = D.recp + 2 * D.k;
   const s8v op = cur;
   uint64_t next = reinterpret_cast<uint64_t>(rec + 2);
   asm volatile("" : "+s"(next) : "s"(op));

@@ -28,18 +28,22 @@ def main():
                    "(tools/gpu_r05_stall.sh, two --pmc passes per size; tools/stall_summary.py); raw counter sums",
            "sizes": {}}
     for size, ops, tag in (("1250", 1250 * 10000, "d1250"), ("10000", 10000 * 10000, "d10k")):
+        if not os.path.isdir(os.path.join(src, tag + "_a")):
+            continue  # a run that took one size only
         raw = last_pair(os.path.join(src, tag + "_a"))
         raw.update(last_pair(os.path.join(src, tag + "_c")))
         per_op = {k: round(raw[k] / ops, 2) for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_BRANCH", "SQ_INSTS_LDS",
                                                      "SQ_INSTS_SMEM", "SQ_INSTS_VMEM", "SQ_ACTIVE_INST_ANY",
                                                      "SQ_WAVE_CYCLES") if k in raw}
         wc = raw["SQ_WAVE_CYCLES"]
-        issue, wait = raw["SQ_ACTIVE_INST_ANY"] / wc, raw["SQ_WAIT_ANY"] / wc
+        # a wave's cycle is one of: issuing, waiting on s_waitcnt, waiting for an
+        # issue slot; what those three leave is the rest (on gfx950 next to nothing)
+        issue, wait, slot = raw["SQ_ACTIVE_INST_ANY"] / wc, raw["SQ_WAIT_ANY"] / wc, raw["SQ_WAIT_INST_ANY"] / wc
         res["sizes"][size] = {"ops": float(ops), "raw": raw, "per_op": per_op, "fraction_of_wave_cycles": {
             "issuing (SQ_ACTIVE_INST_ANY)": round(issue, 3),
             "waiting on s_waitcnt (SQ_WAIT_ANY)": round(wait, 3),
-            "waiting for an issue slot with a ready instruction (SQ_WAIT_INST_ANY)": round(raw["SQ_WAIT_INST_ANY"] / wc, 3),
-            "rest (dependency latency, hazards, branch resolution)": round(1 - issue - wait, 3)}}
+            "waiting for an issue slot with a ready instruction (SQ_WAIT_INST_ANY)": round(slot, 3),
+            "rest (not issuing and in neither wait)": round(1 - issue - wait - slot, 3)}}
     json.dump(res, open(dst, "w"), indent=1)
     print(json.dumps({s: v["fraction_of_wave_cycles"] for s, v in res["sizes"].items()}))
 
