@@ -135,11 +135,6 @@ __device__ __forceinline__ void ch_store(const Regs<kChE, K>& R, const ChunkArgs
   }
 }
 
-// op records: 1 = 64 at a time through vector loads, 0 = scalar loads one ahead
-#ifndef MTE_CH_VREC
-#define MTE_CH_VREC 1
-#endif
-
 // 64 op records from record `base` on: lane l holds record base + l, one
 // dword per register
 __device__ __forceinline__ void ch_rec_batch(uint32_t (&b)[8], const uint4* recp, uint32_t base) {
@@ -410,24 +405,19 @@ __device__ int ch_ops(DocRun& D, const ReplayArgs& a, const ChunkArgs& ch, uint3
   const uint32_t ng = (uint32_t)((nch + kChGroup - 1) / kChGroup);
   uint32_t* cnt = ch.cnt + (uint64_t)doc * ch.nch_cap;
   const bool newcalc = (D.flags & MTE_DOC_NEW_LENGTH_CALC) != 0;
-  // MTE_CH_VREC: op records 64 at a time through vector loads (lane l:
+  // op records 64 at a time through vector loads (lane l:
   // record base + l), the next batch loading while this one is used, so the
   // LDS scans never wait behind a scalar load in flight (SMEM and LDS share
   // lgkmcnt).  Past the doc's last op the loads read the next doc's records
   // or the zeroed tail (kRecPad).
-#if MTE_CH_VREC
   uint32_t rbase = D.k & ~(uint32_t)(kWave - 1);
   uint32_t rc0[8], rc1[8];
   ch_rec_batch(rc0, D.recp, rbase);
   ch_rec_batch(rc1, D.recp, rbase + kWave);
-#else
-  s8v cur = sload8(D.recp + 2 * D.k);
-#endif
   while (D.k < D.k1) {
     if constexpr (S) {
       if (st[kStOps] >= 256) run_flush_stats(D, st, a);
     }
-#if MTE_CH_VREC
     if (D.k - rbase >= (uint32_t)kWave) {  // the next batch; load the one after
       rbase += kWave;
 #pragma unroll
@@ -437,14 +427,6 @@ __device__ int ch_ops(DocRun& D, const ReplayArgs& a, const ChunkArgs& ch, uint3
     s8v op;
 #pragma unroll
     for (int i = 0; i < 8; i++) op[i] = (int32_t)rdlane(rc0[i], (int)(D.k - rbase));
-#else
-    // this op's record was prefetched; the next one is in flight meanwhile
-    // (past the last op it reads the next doc's record or the zeroed tail)
-    const s8v op = cur;
-    uint64_t next = uni64(reinterpret_cast<uint64_t>(D.recp + 2 * (D.k + 1)));
-    asm volatile("" : "+s"(next) : "s"(op));
-    cur = sload8(reinterpret_cast<const uint4*>(next));
-#endif
     CHPROF(uint64_t tq = ch_clock(); uint64_t tn;)
     if (MTE_CH_PREFETCH && lane_id() == 0) *(volatile int32_t*)&ctl->pf_k = (int32_t)D.k;
     const uint32_t w3 = (uint32_t)op[3];

@@ -34,10 +34,8 @@ using namespace mte;
 namespace {
 
 // reset resume/escalation flags and stats at the start of a batch
-__global__ void begin_batch_kernel(DocHdr* hdr, unsigned long long* stats, uint32_t n_docs,
-                                   unsigned long long* gdone) {
+__global__ void begin_batch_kernel(DocHdr* hdr, unsigned long long* stats, uint32_t n_docs) {
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d == 0) *gdone = 0;
   if (d >= n_docs) return;
   hdr[d].resume = 0;
   hdr[d].flags &= ~(kHdrNeedsEsc | kHdrTreeEsc | kHdrTreeBig | kHdrRel);
@@ -558,8 +556,7 @@ struct mte_ctx {
   // diagnostics: MTE_WAVE_CLOCK=<file> dumps pass-1 start / end times per
   // pair (s_memrealtime, 100 MHz) at every mte_sync
   unsigned long long* d_wclock = nullptr;
-  unsigned long long* d_gdone = nullptr;  // pass-1 global progress (fair priority)
-  double last_ms = 0, last_ops = 0;       // previous run (pass-1 schedule estimate, MTE_FAIR_PRIO 4)
+  double last_ms = 0, last_ops = 0;  // previous run (pass-1 schedule estimate)
   const char* wclock_path = nullptr;
 
   // chunked big-document pass (seg_capacity >= kChunkMinCap, mte_chunk.h)
@@ -1225,7 +1222,7 @@ int mte_destroy(mte_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   free_docs(c);
-  void* ps[] = {c->arena, c->d_pow, c->d_gdone, c->d_hprof};
+  void* ps[] = {c->arena, c->d_pow, c->d_hprof};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   for (int w = 0; w < 2; w++) {
@@ -1748,9 +1745,8 @@ int mte_run(mte_ctx* c) {
   if (!c->n_docs) return MTE_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));  // kernel_ms covers every kernel of the run
-  if (!c->d_gdone) HIPCHK(c, hipMalloc((void**)&c->d_gdone, 64));
   hipLaunchKernelGGL(begin_batch_kernel, dim3((c->n_docs + 255) / 256), dim3(256), 0, c->stream, c->hdr, c->stats,
-                     c->n_docs, c->d_gdone);
+                     c->n_docs);
   HIPCHK(c, hipGetLastError());
   ReplayArgs a;
   a.hdr = c->hdr;
@@ -1770,8 +1766,6 @@ int mte_run(mte_ctx* c) {
   a.n_pairs = c->n_pairs;
   a.group = c->pass1_group;
   a.wclock = nullptr;
-  a.gdone = c->d_gdone;
-  a.n_ops = c->n_ops;
   const bool evs = !c->h_dl_off_s[c->rslot].empty();
   a.dl = evs ? c->d_dl_s[c->rslot] : nullptr;
   a.dl_off = evs ? c->d_dl_off_s[c->rslot] : nullptr;

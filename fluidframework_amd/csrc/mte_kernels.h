@@ -97,8 +97,6 @@ struct ReplayArgs {
   uint32_t n_pairs;           // pass-1 waves
   uint32_t group;             // pass 1: documents per wave (1 .. kGroupMax)
   unsigned long long* wclock;  // diagnostics (MTE_WAVE_CLOCK): pass-1 start / end time per pair, or null
-  unsigned long long* gdone;   // pass 1: ops applied so far by all waves (fair priority), zeroed per run
-  unsigned long long n_ops;    // ops of the batch
   unsigned long long eta;      // expected pass-1 duration in s_memrealtime ticks (0 = unknown)
   // kPack4 with a side key: the key (< 4) whose value ids may exceed a byte
   // because only marker inserts ever set it (markerId); pass 1 holds a
@@ -157,6 +155,9 @@ __device__ __forceinline__ uint32_t rdlane(uint32_t v, int lane) {
 }
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+  return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32);
+}
 
 // F[j] with a wave-uniform j.  Each element passes through an empty asm so
 // the select chain stays on register values: a chain of selects on loads

@@ -21,49 +21,20 @@
 #include "mte_kernels.h"
 
 // Build-time knobs (tools/variants.sh builds A/B variants; defaults are the product build).
-// MTE_FAIR_PRIO: 0 = hardware age order, 1 = 4 linear bands of work left, 2 = geometric bands,
-// 3 = bands around the global progress (one returning atomic per burst; measured 33.9 ms vs
-// 23.9 ms on config 3: the single contended counter costs more than the balance gains),
-// 4 = bands around the previous run's schedule (product: 22.6 ms; band 1 on the first run).
 #ifndef MTE_PAIR_WAVES  // pass-1 waves per SIMD the register budget is sized for (5: 96 VGPRs, 4: 128)
 #define MTE_PAIR_WAVES 5
 #endif
 #ifndef MTE_BURST
 #define MTE_BURST 128
 #endif
-#ifndef MTE_PASS1_EMAX
+#ifndef MTE_PASS1_EMAX  // largest pass-1 register tier (4, or 2: documents over 126 segments go to pass 2)
 #define MTE_PASS1_EMAX 4
-#endif
-#ifndef MTE_FAIR_PRIO  // pass-1 issue priority policy (below)
-#define MTE_FAIR_PRIO 4
-#endif
-#ifndef MTE_VREC  // 1: pass-1 op records fetched with vector loads (vmcnt), 0: scalar loads (lgkmcnt)
-// 1 since round 6 (profiles/r06/ab/vrec/): config 3 at 10k documents 22.3 -> 21.6 ms (an LDS wait
-// no longer waits for the next record's scalar load too); 1,250 documents 8.01 -> 8.07 ms
-#define MTE_VREC 1
-#endif
-#ifndef MTE_E1_DPP  // 1: the E = 1 shift moves slots with DPP instead of ds_bpermute
-#define MTE_E1_DPP 0
-#endif
-#ifndef MTE_OUTLINE  // 1: pass-1 tiers as out-of-line functions (measured: same time, 1.7x the HBM traffic)
-#define MTE_OUTLINE 0
-#endif
-#ifndef MTE_STEPV_EMAX  // tiers up to this E run the per-slot-flag step (doc_step_v), larger ones doc_step
-#define MTE_STEPV_EMAX 4
-#endif
-#ifndef MTE_EARLY_PROPS  // 1: pass-1 tiers load an op's compiled propset at the op's start
-#define MTE_EARLY_PROPS 0
-#endif
-#ifndef MTE_DIAG_NOPAYLOAD  // diagnostics only (wrong results): pass-1 tiers skip the text-offset / property planes
-#define MTE_DIAG_NOPAYLOAD 0
-#endif
-#ifndef MTE_OUTLINE_E4  // 1: only the rare E = 4 tier out of line (the E <= 2 loops get the registers)
-#define MTE_OUTLINE_E4 0
 #endif
 
 namespace mte {
 
 constexpr uint32_t kBurst = MTE_BURST;  // ops per burst in pass 1
+constexpr int kStepVEmax = 4;           // tiers up to this E run the per-slot-flag step (doc_step_v), larger ones doc_step
 
 // per-document replay state (wave-uniform); op cursors are 32-bit, relative
 // to the document's first record of the batch
@@ -95,22 +66,6 @@ __device__ __forceinline__ s8v sload8(const uint4* p) { return *(cs8p)(const voi
 // compiled propset `psi` (mte_kernels.h)
 __device__ __forceinline__ s8v sload_props(const ReplayArgs& a, uint32_t psi) { return sload8(a.cps + 2 * psi); }
 
-// op record through a vector load: dword i in lane i < 8.  Its wait is on
-// vmcnt, so the LDS traffic of an op (shift permutes, zamboni) never waits for
-// the next record as it does for a scalar load in flight (SMEM and LDS share
-// lgkmcnt, and SMEM returns out of order, so any LDS wait becomes lgkmcnt(0)).
-// Every lane loads (lanes >= 8 repeat lanes 0-7, the same cache line), so the
-// load needs no change of the exec mask around it; only lanes 0-7 are read.
-__device__ __forceinline__ uint32_t vload_rec8(const uint4* rec) {
-  return reinterpret_cast<const uint32_t*>(rec)[__lane_id() & 7];
-}
-#if MTE_VREC
-typedef uint32_t RecV;  // the prefetched record of the pass-1 tiers (doc_step_v)
-#else
-typedef s8v RecV;
-#endif
-__device__ __forceinline__ void swait(s8v&) {}
-
 // L2 prefetch: lane l touches record `from + 4 l` (one 128-B line per lane,
 // 256 records).  The loaded word is folded into `sink` one prefetch later, so
 // the wait for it never stalls.
@@ -126,10 +81,6 @@ __device__ __forceinline__ void touch_records(const DocRun& D, uint32_t from, ui
 // the compiled propset record; longer sets are read here.  Applied to the slots with
 // sel[j] set (E slots per lane, K planes); no lambdas, so the register arrays
 // never need an address.
-#ifndef MTE_SET_PLANE_SWITCH
-#define MTE_SET_PLANE_SWITCH 1
-#endif
-
 template <int E>
 __device__ __forceinline__ void set_one_plane(uint32_t (&p)[E], const bool (&sel)[E], uint32_t val) {
 #pragma unroll
@@ -150,9 +101,10 @@ __device__ __forceinline__ void set_plane(uint32_t (&pr)[kRP<K>][E], const bool 
     for (int jj = 0; jj < E; jj++) pr[0][jj] = sel[jj] ? ((pr[0][jj] & keep) | v) : pr[0][jj];
     return;
   }
-#if MTE_SET_PLANE_SWITCH
   // `key` is wave-uniform: one scalar branch picks the plane, so only that
-  // plane's E selects issue (the branch-free form costs K x E selects)
+  // plane's E selects issue (a branch-free form costs K x E selects, and a
+  // `kk == key` test per plane gets folded into pr[key], a dynamic index that
+  // would push the whole register file to scratch)
   switch (key) {
     case 0: if constexpr (K > 0) set_one_plane<E>(pr[K > 0 ? 0 : 0], sel, val); break;
     case 1: if constexpr (K > 1) set_one_plane<E>(pr[K > 1 ? 1 : 0], sel, val); break;
@@ -164,16 +116,6 @@ __device__ __forceinline__ void set_plane(uint32_t (&pr)[kRP<K>][E], const bool 
     case 7: if constexpr (K > 7) set_one_plane<E>(pr[K > 7 ? 7 : 0], sel, val); break;
     default: break;
   }
-#else
-  // branch-free over planes: a `kk == key` branch gets folded into pr[key],
-  // a dynamic index that would push the whole register file to scratch
-#pragma unroll
-  for (int kk = 0; kk < K; kk++) {
-    const bool hit = (uint32_t)kk == key;
-#pragma unroll
-    for (int jj = 0; jj < E; jj++) pr[kk][jj] = (hit && sel[jj]) ? val : pr[kk][jj];
-  }
-#endif
 }
 
 template <int E, int K>
@@ -229,34 +171,11 @@ __device__ __forceinline__ void shift_apply(T (&F)[E], const uint32_t (&p1)[NF],
 // old[i - d(i)] with d(i) = (i > t1) + (i > t2), as pull_shift does for one
 // plane.  The cross-lane moves of all planes are issued first and the selects
 // after, so no DPP read waits on the VALU write just before it (a chained
-// move per plane costs two hazard nops each).
-template <int E, typename T>
-__device__ __forceinline__ void shift_perm(T (&F)[E], int addr) {
-  F[0] = (T)__builtin_amdgcn_ds_bpermute(addr, (int32_t)F[0]);
-}
-
+// move per plane costs two hazard nops each).  For the tiers of doc_step
+// (E > 1; shift_v, mte_step1.h, is the same shift on per-slot flags).
 template <int E, int K, bool LP>
 __device__ __forceinline__ void shift_all(Regs<E, K>& R, int32_t (&L)[E], int32_t (&P)[E], int t1, int t2) {
-  if constexpr (E == 1) {
-    // one slot per lane: lane l pulls lane l - d(l) through the LDS crossbar
-    // (ds_bpermute: one LDS-pipe instruction per plane instead of two DPP
-    // moves and two selects on the VALU)
-    const int l = lane_id();
-    const int addr = (l - (l > t1 ? 1 : 0) - (l > t2 ? 1 : 0)) << 2;
-    shift_perm<E>(R.len, addr);
-    shift_perm<E>(R.seq, addr);
-    shift_perm<E>(R.rseq, addr);
-    shift_perm<E>(R.rmask, addr);
-    shift_perm<E>(R.meta, addr);
-    shift_perm<E>(R.toff, addr);
-#pragma unroll
-    for (int k = 0; k < kRegPlanes<K>; k++) shift_perm<E>(R.pr[k], addr);
-    if constexpr (LP) {
-      shift_perm<E>(L, addr);
-      shift_perm<E>(P, addr);
-    }
-    return;
-  }
+  static_assert(E >= 2, "one slot per lane shifts with ds_bpermute (shift_v)");
   constexpr int NF = kFieldPlanes + kRegPlanes<K> + (LP ? 2 : 0);
   uint32_t last[NF], last2[NF];
   shift_grab<E, NF>(last, last2, 0, R.len);
@@ -275,7 +194,7 @@ __device__ __forceinline__ void shift_all(Regs<E, K>& R, int32_t (&L)[E], int32_
 #pragma unroll
   for (int f = 0; f < NF; f++) p1[f] = (uint32_t)lane_prev((int32_t)last[f]);  // old[base - 1]
 #pragma unroll
-  for (int f = 0; f < NF; f++) p2[f] = (uint32_t)lane_prev((int32_t)(E >= 2 ? last2[f] : p1[f]));  // old[base - 2]
+  for (int f = 0; f < NF; f++) p2[f] = (uint32_t)lane_prev((int32_t)last2[f]);  // old[base - 2]
   const int base = lane_id() * E;
   bool g1[E], g2[E];
 #pragma unroll
@@ -381,6 +300,10 @@ struct SplitPatch {
 // The collab-window error of an applied op, checked in the reference's order:
 // completeAndLogOp (client.ts:525-528), then updateSeqNumbers (937-945) ->
 // setMinSeq (mergeTree.ts:1078-1084), which sets currentSeq before its asserts.
+// The test and update around it stay written out at their four sites (doc_step,
+// doc_step_v, ch_ops, tree_step): folded into a helper that returns error / 0 /
+// "minSeq advanced", the code comes back as selects that the site tests again,
+// and the register allocation of the whole op loop changes with it.
 __device__ __forceinline__ int window_error(DocRun& D, bool live, bool end, int32_t s, int32_t msn) {
   if (live) {
     if (!(D.cur_seq < s)) return MTE_E_SEQ_ORDER;
@@ -393,6 +316,47 @@ __device__ __forceinline__ int window_error(DocRun& D, bool live, bool end, int3
     if (!(D.min_seq <= msn)) return MTE_E_MSN_ORDER;
   }
   return MTE_E_STATE;  // unreachable: the caller saw a violation
+}
+
+// zamboni of a register-resident document at E > 1 slots per lane: drop the
+// tombstones with removedSeq <= msn (padding included) by a stream compaction
+// staged through LDS.  Returns the new segment count (n: nothing dropped).
+template <int E, int K>
+__device__ __forceinline__ int zamboni_lds(Regs<E, K>& R, int n, int32_t msn, uint32_t* zlds) {
+  bool keep[E];
+  int32_t cntl = 0;
+#pragma unroll
+  for (int jj = 0; jj < E; jj++) {
+    keep[jj] = R.rseq[jj] > msn;
+    cntl += keep[jj] ? 1 : 0;
+  }
+  const int32_t incl = wave_incl_scan(cntl);
+  const int n_new = rdlane(incl, kWave - 1);
+  if (n_new != n) {
+    int32_t dst[E];
+    int32_t d0 = incl - cntl;
+#pragma unroll
+    for (int jj = 0; jj < E; jj++) {
+      dst[jj] = d0;
+      d0 += keep[jj] ? 1 : 0;
+    }
+    compact_plane<E>(R.len, keep, dst, zlds);
+    compact_plane<E>(R.seq, keep, dst, zlds);
+    compact_plane<E>(R.rseq, keep, dst, zlds);
+    compact_plane<E>(R.rmask, keep, dst, zlds);
+    compact_plane<E>(R.meta, keep, dst, zlds);
+    compact_plane<E>(R.toff, keep, dst, zlds);
+#pragma unroll
+    for (int kk = 0; kk < kRegPlanes<K>; kk++) compact_plane<E>(R.pr[kk], keep, dst, zlds);
+    const int base = lane_id() * E;
+#pragma unroll
+    for (int jj = 0; jj < E; jj++) {
+      const bool pad = base + jj >= n_new;
+      R.rseq[jj] = pad ? kPad : R.rseq[jj];
+      R.len[jj] = pad ? 0 : R.len[jj];
+    }
+  }
+  return n_new;
 }
 
 // One op record of one document: Client.applyMsg -> applyRemoteOp ->
@@ -632,39 +596,8 @@ __device__ __forceinline__ int doc_step(Regs<E, K>& R, DocRun& D, uint32_t (&st)
     D.cur_seq = s;
     if (msn > D.min_seq) {
       D.min_seq = msn;
-      // zamboni: drop tombstones with removedSeq <= minSeq (padding included)
-      // by a stream compaction staged through LDS
-      bool keep[E];
-      int32_t cntl = 0;
-#pragma unroll
-      for (int jj = 0; jj < E; jj++) {
-        keep[jj] = R.rseq[jj] > msn;
-        cntl += keep[jj] ? 1 : 0;
-      }
-      const int32_t incl = wave_incl_scan(cntl);
-      const int n_new = rdlane(incl, kWave - 1);
+      const int n_new = zamboni_lds<E, K>(R, n, msn, zlds);
       if (n_new != n) {
-        int32_t dst[E];
-        int32_t d0 = incl - cntl;
-#pragma unroll
-        for (int jj = 0; jj < E; jj++) {
-          dst[jj] = d0;
-          d0 += keep[jj] ? 1 : 0;
-        }
-        compact_plane<E>(R.len, keep, dst, zlds);
-        compact_plane<E>(R.seq, keep, dst, zlds);
-        compact_plane<E>(R.rseq, keep, dst, zlds);
-        compact_plane<E>(R.rmask, keep, dst, zlds);
-        compact_plane<E>(R.meta, keep, dst, zlds);
-        compact_plane<E>(R.toff, keep, dst, zlds);
-#pragma unroll
-        for (int kk = 0; kk < kRegPlanes<K>; kk++) compact_plane<E>(R.pr[kk], keep, dst, zlds);
-#pragma unroll
-        for (int jj = 0; jj < E; jj++) {
-          const bool pad = base + jj >= n_new;
-          R.rseq[jj] = pad ? kPad : R.rseq[jj];
-          R.len[jj] = pad ? 0 : R.len[jj];
-        }
         D.n = n_new;
         // drop to a smaller register tier once the doc fits in half of it
         if (E > emin && n_new + 2 + 16 <= 32 * E) return 1;
@@ -733,17 +666,6 @@ __device__ __forceinline__ void run_finish(DocRun& D, const ReplayArgs& a) {
   }
 }
 
-// handle a doc_step result: 0 keep going, otherwise the doc leaves the loop
-__device__ __forceinline__ bool step_done(DocRun& D, int rc) {
-  if (rc < 0) {
-    D.status = rc;
-    D.running = false;
-    return true;
-  }
-  if (D.k >= D.k1) D.running = false;
-  return rc != 0 || !D.running;
-}
-
 // One burst of up to `limit` ops of one document at register tier E: load
 // its segments into VGPRs, replay, write them back.  Returns early when the
 // document needs another tier or stops.
@@ -751,7 +673,7 @@ template <int E, int K, bool S>
 __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32_t* zlds, int emin, uint32_t limit) {
   Regs<E, K> R;
   uint32_t st[kNumStats] = {};
-  if constexpr (E <= MTE_STEPV_EMAX) {
+  if constexpr (E <= kStepVEmax) {
     // pass 1 reads `a` in place (args_in_place).  What every step reads of it
     // (cps, side_key, cap) the compiler hoists out of the op loop itself;
     // text_base is first read under the step's insert branch and would be
@@ -762,15 +684,18 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   load_regs<E, K>(R, D, a);
   const uint32_t kend = D.k1 - D.k > limit ? D.k + limit : D.k1;
   s8v cur;
-  RecV vcur;
+  uint32_t vcur;
   [[maybe_unused]] const uint32_t* vrec = nullptr;  // this lane's dword of the record in vcur
-  if constexpr (E <= MTE_STEPV_EMAX) {
-#if MTE_VREC
+  if constexpr (E <= kStepVEmax) {
+    // the pass-1 tiers read op records through a vector load: dword i in lane
+    // i < 8.  Its wait is on vmcnt, so the LDS traffic of an op (shift
+    // permutes, zamboni) never waits for the next record as it does for a
+    // scalar load in flight (SMEM and LDS share lgkmcnt, and SMEM returns out
+    // of order, so any LDS wait becomes lgkmcnt(0)).  Every lane loads (lanes
+    // >= 8 repeat lanes 0-7, the same cache line), so the load needs no change
+    // of the exec mask around it; only lanes 0-7 are read.
     vrec = reinterpret_cast<const uint32_t*>(D.recp + 2 * D.k) + (lane_id() & 7);
     vcur = *vrec;
-#else
-    vcur = sload8(D.recp + 2 * D.k);
-#endif
   } else {
     cur = sload8(D.recp + 2 * D.k);
   }
@@ -784,7 +709,7 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   for (;;) {
     if (!per_burst && (D.k & (kTouchSpan / 2 - 1)) == 0) touch_records(D, D.k + kTouchSpan / 2, pending, sink);
     int rc;
-    if constexpr (E <= MTE_STEPV_EMAX) rc = doc_step_v<E, K, S>(R, D, st, vcur, vrec, a, zlds, emin);
+    if constexpr (E <= kStepVEmax) rc = doc_step_v<E, K, S>(R, D, st, vcur, vrec, a, zlds, emin);
     else rc = doc_step<E, K, S>(R, D, st, cur, a, zlds, emin);
     if (rc != 0) {
       if (rc < 0) {
@@ -796,10 +721,6 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
     if (D.k >= kend) break;
   }
   if (D.k >= D.k1) D.running = false;
-  if constexpr (E > MTE_STEPV_EMAX) swait(cur);  // no scalar load may be left in flight
-#if !MTE_VREC
-  if constexpr (E <= MTE_STEPV_EMAX) swait(vcur);
-#endif
   store_regs<E, K>(R, D, a);
   if constexpr (S) run_flush_stats(D, st, a);
   sink ^= pending;
@@ -816,112 +737,22 @@ __device__ __forceinline__ int pick_pass1_tier(DocRun& D, uint32_t cap) {
   }
   if (D.n + 2 <= kWave) return 1;
   if (D.n + 2 <= 2 * kWave) return 2;
-  if (MTE_PASS1_EMAX == 3 && D.n + 2 <= 3 * kWave) return 3;
   if (MTE_PASS1_EMAX >= 4 && D.n + 2 <= 4 * kWave) return 4;
   D.flags |= kHdrNeedsEsc;  // continue in the big-doc pass
   D.running = false;
   return 0;
 }
 
-// ---- out-of-line pass-1 bursts (MTE_OUTLINE=1, an A/B variant) -------------
-// Each register tier as its own (non-inlined) function, so the register
-// allocator sizes each tier's op loop on its own: inlined together, the E = 4
-// tier's pressure leaves spill code in the E = 1 / 2 loops.  Measured on
-// config 3 (profiles/r01): no change in time (the spills are off the per-op
-// dependency chain) and 1.7x the HBM traffic (caller/callee register saves per
-// burst), so the product build inlines.  Arguments arrive in VGPRs under the
-// call ABI; every one is wave-uniform, so it is made scalar again at entry.
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32);
-}
-template <typename T>
-__device__ __forceinline__ T* unip(T* p) {
-  return reinterpret_cast<T*>(uni64(reinterpret_cast<uint64_t>(p)));
-}
-
-__device__ __forceinline__ ReplayArgs uni_args(const ReplayArgs& a) {
-  ReplayArgs u;
-  u.hdr = unip(a.hdr);
-  u.planes = unip(a.planes);
-  u.stride = uni64(a.stride);
-  u.cap = uni(a.cap);
-  u.n_docs = uni(a.n_docs);
-  u.recs = unip(a.recs);
-  u.cps = unip(a.cps);
-  u.op_off = unip(a.op_off);
-  u.ps = unip(a.ps);
-  u.pe = unip(a.pe);
-  u.n_keys = uni(a.n_keys);
-  u.text_base = uni(a.text_base);
-  u.stats = unip(a.stats);
-  u.pair_docs = unip(a.pair_docs);
-  u.n_pairs = uni(a.n_pairs);
-  return u;
-}
-
-struct BurstState {  // the mutable part of DocRun
-  int32_t n, min_seq, cur_seq, status;
-  uint32_t flags, k;
-  int32_t running;
-};
-
-typedef __attribute__((address_space(3))) uint32_t* lds_u32p;
-
-template <int E, int K, bool S>
-__device__ __attribute__((noinline)) BurstState burst_call(BurstState io, int doc, const uint4* recp, uint32_t k1,
-                                                           ReplayArgs a0, lds_u32p zl) {
-  const ReplayArgs a = uni_args(a0);
-  DocRun D;
-  D.doc = uni((int32_t)doc);
-  D.recp = unip(recp);
-  D.k1 = uni(k1);
-  D.n = uni(io.n);
-  D.min_seq = uni(io.min_seq);
-  D.cur_seq = uni(io.cur_seq);
-  D.status = uni(io.status);
-  D.flags = uni(io.flags);
-  D.k = uni(io.k);
-  D.running = uni(io.running) != 0;
-  burst_run<E, K, S>(D, a, (uint32_t*)zl, 1, kBurst);
-  return BurstState{D.n, D.min_seq, D.cur_seq, D.status, D.flags, D.k, D.running ? 1 : 0};
-}
-
-template <int E, int K, bool S>
-__device__ __forceinline__ void burst_out(DocRun& D, const ReplayArgs& a, uint32_t* zlds) {
-  const BurstState r = burst_call<E, K, S>(BurstState{D.n, D.min_seq, D.cur_seq, D.status, D.flags, D.k,
-                                                      D.running ? 1 : 0},
-                                           D.doc, D.recp, D.k1, a, (lds_u32p)zlds);
-  D.n = uni(r.n);
-  D.min_seq = uni(r.min_seq);
-  D.cur_seq = uni(r.cur_seq);
-  D.status = uni(r.status);
-  D.flags = uni(r.flags);
-  D.k = uni(r.k);
-  D.running = uni(r.running) != 0;
-}
-
 template <int K, bool S>
 __device__ __forceinline__ void pass1_burst(DocRun& D, const ReplayArgs& a, uint32_t* zlds) {
   const int e = pick_pass1_tier(D, a.cap);
-#if MTE_OUTLINE
-  if (e == 1) burst_out<1, K, S>(D, a, zlds);
-  else if (e == 2) burst_out<2, K, S>(D, a, zlds);
-  else if constexpr (MTE_PASS1_EMAX >= 4) {
-    if (e == 4) burst_out<4, K, S>(D, a, zlds);
-  }
-#elif defined(MTE_ISA_STUDY)  // ISA inspection only: one tier
+#if defined(MTE_ISA_STUDY)  // ISA inspection only: one tier
   if (e) burst_run<MTE_ISA_STUDY, K, S>(D, a, zlds, 1, kBurst);
 #else
   if (e == 1) burst_run<1, K, S>(D, a, zlds, 1, kBurst);
   else if (e == 2) burst_run<2, K, S>(D, a, zlds, 1, kBurst);
-  else if constexpr (MTE_PASS1_EMAX == 3) {
-    if (e == 3) burst_run<3, K, S>(D, a, zlds, 1, kBurst);
-  } else if constexpr (MTE_PASS1_EMAX >= 4) {
-#if MTE_OUTLINE_E4
-    if (e == 4) burst_out<4, K, S>(D, a, zlds);
-#else
+  else if constexpr (MTE_PASS1_EMAX >= 4) {
     if (e == 4) burst_run<4, K, S>(D, a, zlds, 1, kBurst);
-#endif
   }
 #endif
 }
@@ -953,32 +784,6 @@ __device__ __forceinline__ void run_to_lds(const DocRun& D, DocHdr* hl) {
   fence_wave();
 }
 
-// Fair issue between the waves sharing a SIMD.  The SIMD arbiter favours the
-// oldest wave, so with equal work per wave the youngest starves, then runs
-// alone (latency-bound) at the end: measured on config 3 the pass-1 waves
-// ended in five steps by dispatch order, 14.9 ms to 26.3 ms (tools/
-// wave_clock.py).  Setting the priority from the work left (4 levels) keeps
-// the waves of a SIMD abreast, so they finish together.
-__device__ __forceinline__ void fair_prio(uint32_t left, uint32_t total) {
-  if constexpr (MTE_FAIR_PRIO == 1) {
-    const uint32_t q = (uint32_t)(((uint64_t)left * 4u) / (total ? total : 1u));
-    if (q >= 3) __builtin_amdgcn_s_setprio(3);
-    else if (q == 2) __builtin_amdgcn_s_setprio(2);
-    else if (q == 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-  } else if constexpr (MTE_FAIR_PRIO >= 3) {
-    // (pair_kernel computes the level itself)
-  } else if constexpr (MTE_FAIR_PRIO == 2) {
-    // geometric bands (> 1/4, > 3/32, > 1/32 of the work left): the last band,
-    // where the waves fall back to age order, is short
-    const uint64_t l32 = (uint64_t)left * 32u, t = total ? total : 1u;
-    if (l32 > 8 * t) __builtin_amdgcn_s_setprio(3);
-    else if (l32 > 3 * t) __builtin_amdgcn_s_setprio(2);
-    else if (l32 > t) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-  }
-}
-
 // The kernel's ReplayArgs, read in place from the kernel argument segment (they
 // are the kernel's first argument).  Taken by value, every field is loaded at
 // the kernel's entry and then lives in an SGPR for the whole kernel, or in a
@@ -997,7 +802,15 @@ __device__ __forceinline__ const ReplayArgs& args_in_place() {
 // pass 1: `a.group` documents per wavefront (1 when the batch fits the chip
 // at one per wave), replayed in turn one burst each, so a 10k-document batch is
 // resident on the chip at once with the register budget of one document
-// (E <= 4); W = waves per SIMD the register budget is sized for
+// (E <= 4); W = waves per SIMD the register budget is sized for.
+//
+// Fair issue between the waves sharing a SIMD: the SIMD arbiter favours the
+// oldest wave, so with equal work per wave the youngest starves, then runs
+// alone (latency-bound) at the end: measured on config 3 the pass-1 waves
+// ended in five steps by dispatch order, 14.9 ms to 26.3 ms (tools/
+// wave_clock.py).  After every burst the wave sets its priority (4 levels)
+// from its progress against the schedule of the previous run, which keeps the
+// waves of a SIMD abreast, so they finish together.
 template <int K, bool S, int WPB, int W>
 __global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayArgs) {
   const ReplayArgs& a = args_in_place();
@@ -1011,7 +824,7 @@ __global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayAr
   DocHdr* hl = hl_all[w];
   uint32_t* zlds = zlds_all[w];
   uint32_t live = 0;  // bit t: document t still has ops to run in this pass
-  uint32_t total = 0;  // ops of the group in this pass, and those left (for fair_prio)
+  uint32_t total = 0;  // ops of the group in this pass, and those left (for the issue priority)
   for (int t = 0; t < g; t++) {
     const int doc = (int)a.pair_docs[(uint32_t)g * (uint32_t)pair + (uint32_t)t];
     if (doc >= 0) {
@@ -1028,9 +841,8 @@ __global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayAr
   fence_wave();
   total = uni(total);
   uint32_t left = total;
-  [[maybe_unused]] const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-  if constexpr (MTE_FAIR_PRIO == 4) __builtin_amdgcn_s_setprio(2);
-  else fair_prio(left, total);
+  const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+  __builtin_amdgcn_s_setprio(2);
   // one burst per iteration, the documents in turn; a single copy of the
   // burst code serves them all (the document is a runtime index)
   for (int t = 0; live; t = (t + 1 == g) ? 0 : t + 1) {
@@ -1043,36 +855,18 @@ __global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayAr
     if (!D.running) live &= ~(1u << t);
     const uint32_t ran = uni(hl[t].resume - k0);
     left -= ran;
-    if constexpr (MTE_FAIR_PRIO == 3) {
-      // progress relative to all waves: the global count of applied ops comes
-      // back from the atomic that adds this burst (its old value)
-      unsigned long long gl = 0;
-      if (lane_id() == 0) gl = atomicAdd(a.gdone, (unsigned long long)ran);
-      gl = ((unsigned long long)uni((uint32_t)(gl >> 32)) << 32) | uni((uint32_t)gl);
-      const unsigned long long mine = (unsigned long long)(total - left) * a.n_ops;  // my fraction x n_ops x total
-      const unsigned long long all = gl * total;
-      const unsigned long long band = (unsigned long long)total * a.n_ops / 64;  // 1/64 of the work
-      if (mine + band < all) __builtin_amdgcn_s_setprio(3);
-      else if (mine < all) __builtin_amdgcn_s_setprio(2);
-      else if (mine < all + band) __builtin_amdgcn_s_setprio(1);
+    // against the schedule of the previous run (a.eta ticks for the whole
+    // pass; a first run's is estimated from the batch, mte_run): behind it ->
+    // higher priority
+    if (a.eta) {
+      const unsigned long long el = __builtin_amdgcn_s_memrealtime() - t_start;
+      const unsigned long long mine = (unsigned long long)(total - left) * a.eta;  // done/total vs el/eta
+      const unsigned long long sched = el * total;
+      const unsigned long long band = (unsigned long long)total * a.eta / 32;
+      if (mine + band < sched) __builtin_amdgcn_s_setprio(3);
+      else if (mine < sched) __builtin_amdgcn_s_setprio(2);
+      else if (mine < sched + band) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-    } else if constexpr (MTE_FAIR_PRIO == 4) {
-      // against the schedule of the previous run (a.eta ticks for the whole
-      // pass): behind it -> higher priority; without an estimate, by work left
-      if (a.eta) {
-        const unsigned long long el = __builtin_amdgcn_s_memrealtime() - t_start;
-        const unsigned long long mine = (unsigned long long)(total - left) * a.eta;  // done/total vs el/eta
-        const unsigned long long sched = el * total;
-        const unsigned long long band = (unsigned long long)total * a.eta / 32;
-        if (mine + band < sched) __builtin_amdgcn_s_setprio(3);
-        else if (mine < sched) __builtin_amdgcn_s_setprio(2);
-        else if (mine < sched + band) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      } else {
-        fair_prio(left, total);
-      }
-    } else {
-      fair_prio(left, total);
     }
   }
   if (lane_id() == 0) {

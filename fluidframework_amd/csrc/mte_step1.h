@@ -83,9 +83,7 @@ __device__ __forceinline__ void perm_plane(T (&F)[E], int addr) {
   F[0] = perm1(F[0], addr);
 }
 
-#ifndef MTE_SHIFT_SEQ_EMIN  // tiers with E >= this shift one plane at a time (register-light)
-#define MTE_SHIFT_SEQ_EMIN 4
-#endif
+constexpr int kShiftSeqEmin = 4;  // tiers with E >= this shift one plane at a time (register-light)
 
 // one plane of shift_v: its two cross-lane moves, then its selects.  The E = 4
 // tier shifts plane by plane: moving all 13 planes' neighbours first needs 52
@@ -103,57 +101,40 @@ __device__ __forceinline__ void shift_plane(T (&F)[E], const bool (&g1)[E], cons
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void shift1_dpp(T (&F)[1], bool g1, bool g2) {
-  const int32_t p1 = lane_prev((int32_t)F[0]);
-  const int32_t p2 = lane_prev(p1);
-  F[0] = g2 ? (T)p2 : (g1 ? (T)p1 : F[0]);
-}
-
 // new[i] = old[i - d(i)], d = g1 + g2 (g2 implies g1; flag words), for every
-// plane and the NX extra per-slot values X.  E == 1: one ds_bpermute per plane.  E > 1:
-// the two cross-lane moves of every plane first (DPP), then the selects.
+// plane and the NX extra per-slot values X.  E == 1: lane l pulls lane l - d(l)
+// through the LDS crossbar (ds_bpermute: one LDS-pipe instruction per plane
+// instead of two DPP moves and two selects on the VALU).  E > 1: the two
+// cross-lane moves of every plane first (DPP), then the selects.
 template <int E, int K, int NX>
 __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX : 1][E], uint32_t g1w,
                                         uint32_t g2w) {
   bool g1[E], g2[E];
-  if constexpr (E > 1 || MTE_E1_DPP) {
+  if constexpr (E > 1) {
     funpack<E>(g1w, g1);
     funpack<E>(g2w, g2);
   }
-  if constexpr (E == 1 && MTE_E1_DPP) {
-    // new = d == 2 ? old[l-2] : d == 1 ? old[l-1] : old, two wave_shr:1 moves per plane
-    shift1_dpp(R.len, g1[0], g2[0]);
-    shift1_dpp(R.seq, g1[0], g2[0]);
-    shift1_dpp(R.rseq, g1[0], g2[0]);
-    shift1_dpp(R.rmask, g1[0], g2[0]);
-    shift1_dpp(R.meta, g1[0], g2[0]);
-    if constexpr (!MTE_DIAG_NOPAYLOAD) shift1_dpp(R.toff, g1[0], g2[0]);
-#pragma unroll
-    for (int k = 0; k < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); k++) shift1_dpp(R.pr[k], g1[0], g2[0]);
-#pragma unroll
-    for (int x = 0; x < NX; x++) shift1_dpp(X[x], g1[0], g2[0]);
-  } else if constexpr (E == 1) {
+  if constexpr (E == 1) {
     const int addr = (lane_id() - (int)g1w - (int)g2w) << 2;
     perm_plane<E>(R.len, addr);
     perm_plane<E>(R.seq, addr);
     perm_plane<E>(R.rseq, addr);
     perm_plane<E>(R.rmask, addr);
     perm_plane<E>(R.meta, addr);
-    if constexpr (!MTE_DIAG_NOPAYLOAD) perm_plane<E>(R.toff, addr);
+    perm_plane<E>(R.toff, addr);
 #pragma unroll
-    for (int k = 0; k < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); k++) perm_plane<E>(R.pr[k], addr);
+    for (int k = 0; k < kRegPlanes<K>; k++) perm_plane<E>(R.pr[k], addr);
 #pragma unroll
     for (int x = 0; x < NX; x++) perm_plane<E>(X[x], addr);
-  } else if constexpr (E >= MTE_SHIFT_SEQ_EMIN) {
+  } else if constexpr (E >= kShiftSeqEmin) {
     shift_plane<E>(R.len, g1, g2);
     shift_plane<E>(R.seq, g1, g2);
     shift_plane<E>(R.rseq, g1, g2);
     shift_plane<E>(R.rmask, g1, g2);
     shift_plane<E>(R.meta, g1, g2);
-    if constexpr (!MTE_DIAG_NOPAYLOAD) shift_plane<E>(R.toff, g1, g2);
+    shift_plane<E>(R.toff, g1, g2);
 #pragma unroll
-    for (int k = 0; k < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); k++) shift_plane<E>(R.pr[k], g1, g2);
+    for (int k = 0; k < kRegPlanes<K>; k++) shift_plane<E>(R.pr[k], g1, g2);
 #pragma unroll
     for (int x = 0; x < NX; x++) shift_plane<E>(X[x], g1, g2);
   } else {
@@ -179,9 +160,9 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
     shift_apply<E, NF>(R.rseq, p1, p2, 2, g1, g2);
     shift_apply<E, NF>(R.rmask, p1, p2, 3, g1, g2);
     shift_apply<E, NF>(R.meta, p1, p2, 4, g1, g2);
-    if constexpr (!MTE_DIAG_NOPAYLOAD) shift_apply<E, NF>(R.toff, p1, p2, 5, g1, g2);
+    shift_apply<E, NF>(R.toff, p1, p2, 5, g1, g2);
 #pragma unroll
-    for (int k = 0; k < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); k++) shift_apply<E, NF>(R.pr[k], p1, p2, kFieldPlanes + k, g1, g2);
+    for (int k = 0; k < kRegPlanes<K>; k++) shift_apply<E, NF>(R.pr[k], p1, p2, kFieldPlanes + k, g1, g2);
 #pragma unroll
     for (int x = 0; x < NX; x++) shift_apply<E, NF>(X[x], p1, p2, kFieldPlanes + kRegPlanes<K> + x, g1, g2);
   }
@@ -191,20 +172,19 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
 // textSegment.ts:40-48, mergeTreeNodes.ts:602-609)
 template <int E, int K, bool S>
 __device__ __forceinline__ void put_new_v(Regs<E, K>& R, uint32_t atw, const s8v& op, uint32_t c,
-                                          uint32_t flags, const ReplayArgs& a, uint32_t (&st)[kNumStats],
-                                          const s8v* pq) {
+                                          uint32_t flags, const ReplayArgs& a, uint32_t (&st)[kNumStats]) {
   const int32_t s = op[0], pos2 = op[5];
   const bool marker = (flags & MTE_F_MARKER) != 0;
   const int32_t nlen = marker ? 1 : pos2;
   const uint32_t meta = (c + 1u) | (marker ? (1u + (uint32_t)pos2) << 8 : 0u);
   uint32_t toff = marker ? 0u : a.text_base + (uint32_t)op[6];
-  const uint32_t psi = MTE_DIAG_NOPAYLOAD ? MTE_NO_PROPS : (uint32_t)op[7];
+  const uint32_t psi = (uint32_t)op[7];
   uint32_t pr[kRP<K>][1];
   const bool one[1] = {true};
 #pragma unroll
   for (int kk = 0; kk < kRP<K>; kk++) pr[kk][0] = 0;
   if (kKeys<K> > 0 && psi != MTE_NO_PROPS) {
-    const s8v q2 = pq ? *pq : sload_props(a, psi);
+    const s8v q2 = sload_props(a, psi);
     apply_props<1, K>(pr, one, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
     MTE_STAT(st[kStPwrites] += (uint32_t)q2[3];)
     if constexpr (K == kPack4) {
@@ -253,7 +233,7 @@ template <int E, int K, bool S, bool CH>
 __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, uint32_t type, uint32_t c,
                                         uint32_t flags, int32_t m, bool newcalc, int32_t off, bool last,
                                         int32_t& tot, int32_t& dlen, const ReplayArgs& a,
-                                        uint32_t (&st)[kNumStats], const s8v* pq = nullptr) {
+                                        uint32_t (&st)[kNumStats]) {
   const int base = lane_id() * E;
   const int32_t s = op[0], r = op[1];
   const int32_t pos1 = op[4] - (CH ? off : 0);
@@ -325,7 +305,7 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
       MTE_STAT(st[kStWritten] += 1;)
     }
     at = vpin(at);
-    if (nlen > 0) put_new_v<E, K, S>(R, at, op, c, flags, a, st, pq);
+    if (nlen > 0) put_new_v<E, K, S>(R, at, op, c, flags, a, st);
     if constexpr (CH) dlen = nlen > 0 ? nlen : 0;
   } else {
     // markRangeRemoved / annotateRange: ensureIntervalBoundary at both ends
@@ -424,10 +404,10 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
           for (int j = 0; j < E; j++) rl += in[j] ? L[j] : 0;
           dlen = -rdlane(wave_incl_scan(rl), kWave - 1);
         }
-      } else if (cnt > 0 && !MTE_DIAG_NOPAYLOAD) {
+      } else if (cnt > 0) {
         // PropertiesManager.addProperties (segmentPropertiesManager.ts:63-151)
         const uint32_t psi = (uint32_t)op[6];
-        const s8v q2 = pq ? *pq : sload_props(a, psi);
+        const s8v q2 = sload_props(a, psi);
         if (flags & MTE_F_REWRITE) {
 #pragma unroll
           for (int kk = 0; kk < kRegPlanes<K>; kk++)
@@ -453,10 +433,8 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
 }
 
 template <int E, int K, bool S>
-__device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&st)[kNumStats], RecV& cur,
+__device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&st)[kNumStats], uint32_t& cur,
                                           const uint32_t*& vrec, const ReplayArgs& a, uint32_t* zlds, int emin) {
-  const int l = lane_id();
-  const int base = l * E;
   const int lim = kWave * E < (int)a.cap ? kWave * E : (int)a.cap;
   if (D.n + 2 > lim) return 1;
   if constexpr (S) {
@@ -464,21 +442,13 @@ __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&s
   }
 
   // ---- op record (prefetched into `cur`; see doc_step) ----------------------
-#if MTE_VREC
   s8v op;
 #pragma unroll
   for (int i = 0; i < 8; i++) op[i] = (int32_t)rdlane(cur, i);
   // the next record (zeroed pad after the last); vrec is this lane's running
-  // pointer into the records (vload_rec8), so no address is formed per op
+  // pointer into the records, so no address is formed per op
   vrec += 8;
   cur = *vrec;
-#else
-  const uint4* rec = D.recp + 2 * D.k;
-  const s8v op = cur;
-  uint64_t next = reinterpret_cast<uint64_t>(rec + 2);
-  asm volatile("" : "+s"(next) : "s"(op));
-  cur = sload8(reinterpret_cast<const uint4*>(next));
-#endif
   const uint32_t w3 = (uint32_t)op[3];
   const uint32_t type = w3 & 0xffu, c = (w3 >> 8) & 0xffu, flags = w3 >> 16;
   if (c >= MTE_MAX_CLIENTS) return MTE_E_CLIENT_RANGE;
@@ -491,22 +461,8 @@ __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&s
   if (type <= MTE_OP_ANNOTATE) {
     MTE_STAT(st[kStScanned] += (uint32_t)n;)
     int32_t tot, dlen;
-#if MTE_EARLY_PROPS
-    // the op's compiled propset, loaded before the lengths and the scan so its
-    // latency hides behind them (annotates, and inserts that carry props)
-    s8v q2e;
-    const s8v* pq = nullptr;
-    if constexpr (kKeys<K> > 0) {
-      const uint32_t psi = type == MTE_OP_ANNOTATE ? (uint32_t)op[6] : (uint32_t)op[7];
-      const bool want = type == MTE_OP_ANNOTATE || (type == MTE_OP_INSERT && psi != MTE_NO_PROPS);
-      q2e = sload_props(a, want ? psi : 0u);
-      pq = &q2e;
-    }
-#else
-    const s8v* pq = nullptr;
-#endif
     const int rc = seg_op_v<E, K, S, false>(R, n, op, type, c, flags, D.min_seq, (D.flags & MTE_DOC_NEW_LENGTH_CALC) != 0,
-                                            0, true, tot, dlen, a, st, pq);
+                                            0, true, tot, dlen, a, st);
     if (rc) return rc;
   } else if (type != MTE_OP_NOOP) {
     return MTE_E_INVALID_ARG;
@@ -536,48 +492,18 @@ __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&s
           R.rseq[0] = __builtin_amdgcn_ds_permute(addr, R.rseq[0]);
           R.rmask[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.rmask[0]);
           R.meta[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.meta[0]);
-          if constexpr (!MTE_DIAG_NOPAYLOAD) R.toff[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.toff[0]);
+          R.toff[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.toff[0]);
 #pragma unroll
-          for (int kk = 0; kk < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); kk++)
+          for (int kk = 0; kk < kRegPlanes<K>; kk++)
             R.pr[kk][0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.pr[kk][0]);
-          const bool pad = l >= n_new;
+          const bool pad = lane_id() >= n_new;
           R.rseq[0] = pad ? kPad : R.rseq[0];
           R.len[0] = pad ? 0 : R.len[0];
           D.n = n_new;
         }
       } else {
-        // stream compaction staged through LDS
-        bool keep[E];
-        int32_t cntl = 0;
-#pragma unroll
-        for (int jj = 0; jj < E; jj++) {
-          keep[jj] = R.rseq[jj] > msn;
-          cntl += keep[jj] ? 1 : 0;
-        }
-        const int32_t incl = wave_incl_scan(cntl);
-        const int n_new = rdlane(incl, kWave - 1);
+        const int n_new = zamboni_lds<E, K>(R, n, msn, zlds);
         if (n_new != n) {
-          int32_t dst[E];
-          int32_t d0 = incl - cntl;
-#pragma unroll
-          for (int jj = 0; jj < E; jj++) {
-            dst[jj] = d0;
-            d0 += keep[jj] ? 1 : 0;
-          }
-          compact_plane<E>(R.len, keep, dst, zlds);
-          compact_plane<E>(R.seq, keep, dst, zlds);
-          compact_plane<E>(R.rseq, keep, dst, zlds);
-          compact_plane<E>(R.rmask, keep, dst, zlds);
-          compact_plane<E>(R.meta, keep, dst, zlds);
-          if constexpr (!MTE_DIAG_NOPAYLOAD) compact_plane<E>(R.toff, keep, dst, zlds);
-#pragma unroll
-          for (int kk = 0; kk < (MTE_DIAG_NOPAYLOAD ? 0 : kRegPlanes<K>); kk++) compact_plane<E>(R.pr[kk], keep, dst, zlds);
-#pragma unroll
-          for (int jj = 0; jj < E; jj++) {
-            const bool pad = base + jj >= n_new;
-            R.rseq[jj] = pad ? kPad : R.rseq[jj];
-            R.len[jj] = pad ? 0 : R.len[jj];
-          }
           D.n = n_new;
           // drop to a smaller register tier once the doc fits in half of it
           if (E > emin && n_new + 2 + 16 <= 32 * E) return 1;

@@ -38,8 +38,8 @@ const REF_SLIDE_ON_REMOVE = 0x40, REF_STAY_ON_REMOVE = 0x80, REF_TRANSIENT = 0x1
 const DELTA_REGEN = 0x10;    // MTE_DELTA_REGEN: kind flag of a regenerated op's records
 const ANNOTATE_SLOTS = 32;   // MTE_ANNOTATE_SLOTS: pending local annotate groups tracked per document
 const F_MARKER = 0x1, F_MSG_END = 0x2, F_REWRITE = 0x4, F_LOCAL = 0x8;
-const F_COMBINE = 0x10, COMBINE_PAIR = 0x80000000;
-const F_REGENERATED = 0x20;  // an ack of a regenerated message (include/mte.h)  // incr / consensus value maps (include/mte.h)
+const F_COMBINE = 0x10, COMBINE_PAIR = 0x80000000;  // incr / consensus value maps (include/mte.h)
+const F_REGENERATED = 0x20;  // an ack of a regenerated message (include/mte.h)
 // a value id matching no other, itself included: NaN (matchProperties' !==, include/mte.h)
 const VALUE_UNEQUAL = 0x40000000;
 const LOCAL_SEQ_BASE = 0x40000000; // MTE_LOCAL_SEQ_BASE

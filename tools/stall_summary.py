@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Pass-1 issue / stall summary from tools/gpu_r05_stall.sh's four --pmc runs
+"""Pass-1 issue / stall summary from the four --pmc runs of tools/gpu_r05_stall.sh
+(a single-visit script, removed; last at commit 15e7501)
 (OUT dir with d1250_a, d1250_c, d10k_a, d10k_c): the last pair_kernel dispatch
 of each run (the timed launch of `bench.py --steps 1 --warmup 0`), its counters
 summed over dimensions, per op and as fractions of the waves' cycles.

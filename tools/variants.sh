@@ -3,6 +3,9 @@
 # product library is fluidframework_amd/_lib/libmte.so).  The flat-pass
 # and chunk-pass translation units are rebuilt with the variant's flags and
 # linked with the product's other objects (make -C fluidframework_amd/csrc first).
+# The knobs are the build-time macros of mte_replay.h (MTE_PAIR_WAVES, MTE_BURST,
+# MTE_PASS1_EMAX) and the diagnostic switches of the other passes; the rejected
+# variants DESIGN.md measures were removed after commit 15e7501.
 # Usage: variants.sh name:"flags" ...   e.g. variants.sh w5e2:"-DMTE_PASS1_EMAX=2"
 set -e
 cd "$(dirname "$0")/.."
