@@ -26,49 +26,19 @@
 // with a final gather, so every other kernel sees the flat layout.
 #pragma once
 
+#include "mte_passes.h"
 #include "mte_replay.h"
 
 namespace mte {
 
-constexpr uint32_t kChunkMinCap = 8192;  // ctxs with a smaller capacity use pass 3 = stream_kernel
-constexpr int kChE = 4;                  // slots per lane
-constexpr int kChSlots = kWave * kChE;   // 256 slots per chunk
-constexpr int kChFill = 128;             // segments per chunk after a re-layout
-constexpr int kChGroup = 64;             // chunks per summary group
-constexpr int kChWaves = 8;              // one document per 512-thread workgroup
-constexpr uint32_t kChMaxGroups = 500;   // G in LDS: 32 x 500 x 4 B
 constexpr int32_t kColInvalid = INT32_MIN;
-
-struct ChunkArgs {
-  uint32_t* arena;   // plane p, doc d, chunk i, slot j: arena[p * astride + (d * nch_cap + i) * 256 + j]
-  uint64_t astride;
-  uint32_t nch_cap;  // chunks per doc
-  uint32_t ng_cap;   // groups per doc (<= kChMaxGroups)
-  uint32_t* cnt;     // [doc][nch_cap] segments per chunk
-  uint32_t* kc;      // [doc][nch_cap] re-layout scratch
-  int32_t* sum;      // [doc][MTE_MAX_CLIENTS][nch_cap]
-  // round phases (mte_round.h): with a plan, chunk_kernel replays only the
-  // documents the plan sends op after op, up to their run's end
-  const uint4* plan;      // [doc] x mode, y k0, z k1, w M (null: every escalated doc to its end)
-  const uint32_t* rflag;  // [doc] non-zero: the round phases left the run to this pass
-};
 
 enum : uint32_t { kModeIdle = 0, kModeRound = 1, kModeSeq = 2 };
 
 // wave-0 -> workgroup requests
 enum ChReq : int32_t { kReqNone = 0, kReqRelayout, kReqRebuild, kReqDone };
 
-struct ChCtl {
-  int32_t req, arg_c, arg_r;
-  int32_t n;        // segments of the doc
-  int32_t nch;      // chunks in use
-  int32_t min_seq;  // for the re-layout's zamboni and the rebuilds
-  int32_t status;
-  int32_t part[kChWaves];
-  int32_t rr[MTE_MAX_CLIENTS];  // refSeq each summary column is valid for
-  int32_t pf_k;     // wave 0's current op (the prefetch wave runs ahead of it)
-  int32_t pf_stop;  // wave 0 left its op loop
-};
+// (ChCtl, the workgroup's control block: mte_passes.h)
 
 // Data this kernel writes is read back with agent-scope loads (vector, L1
 // bypassed): never through the scalar cache, never a stale L1 line.

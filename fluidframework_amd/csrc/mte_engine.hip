@@ -17,14 +17,6 @@
 #include <vector>
 
 #include "mte_kernels.h"
-#include "mte_replay.h"
-#include "mte_stream.h"
-#include "mte_chunk.h"
-
-namespace mte {
-}  // namespace mte
-#include "mte_tree.h"
-#include "mte_htree.h"
 #include "mte_passes.h"
 
 #include <rccl/rccl.h>
@@ -517,89 +509,95 @@ struct CommRef {
   std::atomic<int> refs{1};
 };
 
-struct mte_ctx {
-  int device = 0;
-  uint32_t n_keys = 0, kt = 0;  // kt: template planes (0/4/8)
-  uint32_t cap = 1024;
-  uint32_t n_docs = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // the tree pass runs on its own stream beside the flat passes (disjoint
-  // documents), forked after the batch set-up and joined before the read-outs
-  hipStream_t tree_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool ran = false, submitted = false;
-  bool rounds_carried = false;  // a round-phase run laid documents out in the arena since the load / reset
-  bool stats_on = true;
-  std::string err;
+namespace {
 
+// A device buffer that only grows (grow(), doubling) and is freed by hand
+// (free_buf()).  No destructor calls HIP: mte_destroy frees in its own order,
+// before the streams go.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  uint64_t cap = 0;  // elements
+};
+
+template <typename T>
+void free_buf(DevBuf<T>& b) {
+  if (b.p) (void)hipFree(b.p);
+  b = DevBuf<T>{};
+}
+
+// One of the context's two batch slots: mte_submit fills one (validation,
+// pinned staging, DMA on up_stream) while a replay of the other may still run
+// on `stream`; a slot is rewritten only after the last run that read it (ev).
+// The buffers keep their capacities across batches and loads.
+struct BatchSlot {
+  DevBuf<mte_op> ops;      // the records, kRecPad zeroed ones after the last
+  DevBuf<uint4> cps;       // compiled propsets, 2 x uint4 each (props_kernel)
+  DevBuf<uint64_t> off;    // op offsets, n_docs + 1
+  DevBuf<mte_propset> ps;
+  DevBuf<mte_prop> pe;
+  // delta events: region offsets (n_docs + 1, host and device), the events,
+  // their counts; h_dl_off is empty when no document of the batch records events
+  std::vector<uint64_t> h_dl_off;
+  DevBuf<uint64_t> dl_off;
+  DevBuf<mte_delta> dl;
+  DevBuf<uint32_t> dl_n;
+  // the streamed pass's document order (longest batch first, so the longest
+  // chains start first): the event documents of DocState::h_sdocs by this
+  // batch's op count, then the rest; unused without such documents
+  DevBuf<uint32_t> sorder;
+  // the documents with MTE_OP_RELPOS records (upload_ops)
+  std::vector<uint32_t> h_rel;
+  DevBuf<uint32_t> rel;
+  DevBuf<uint32_t> hord;  // the HBM tree pass's candidates, most records first
+  bool hord_ok = false;   // ... of the loaded documents
+  uint64_t n_ops = 0, n_propsets = 0;
+  uint32_t text_base = 0;    // where the batch's text starts in the arena
+  uint64_t max_doc_ops = 0;  // the batch's largest per-document op count
+  hipEvent_t ev = nullptr;   // the last run that read the slot is done
+
+  void release() {
+    free_buf(ops), free_buf(cps), free_buf(off), free_buf(ps), free_buf(pe);
+    free_buf(dl_off), free_buf(dl), free_buf(dl_n);
+    free_buf(sorder), free_buf(rel), free_buf(hord);
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+  }
+};
+
+// the mte_load_segments image (SoA, 6 + kt planes at stride n)
+struct SegImage {
+  uint32_t* img = nullptr;
+  uint32_t* doc = nullptr;
+  uint64_t* off = nullptr;
+  uint64_t n = 0;
+  ImgConst uc = {};  // the image's uniform planes (image_kernel)
+};
+
+// What mte_load_docs creates and the next load (free_docs) drops: nothing here
+// survives a reload.
+struct DocState {
+  uint32_t n_docs = 0;
+  bool rounds_carried = false;  // a round-phase run laid documents out in the arena since the load / reset
   DocHdr* hdr = nullptr;
   SegSoA soa{};
   unsigned long long* stats = nullptr;
   mte_doc_init* d_inits = nullptr;
   uint32_t* d_init_props = nullptr;
-  uint64_t* d_pow = nullptr;  // pow1[32], pow2[32]
-
-  // mte_load_segments image (SoA, 6 + kt planes at stride n_img)
-  uint32_t* d_img = nullptr;
-  uint32_t* d_img_doc = nullptr;
-  uint64_t* d_img_off = nullptr;
-  uint64_t n_img = 0;
-  ImgConst img_uc = {};  // the image's uniform planes (image_kernel)
-
-  // pinned staging for op-record uploads (mte_submit), allocated on first use
-  static constexpr int kStages = 3;
-  static constexpr size_t kStageBytes = 64ull << 20;
-  void* stage[kStages] = {nullptr, nullptr, nullptr};
-  hipEvent_t stage_ev[kStages] = {nullptr, nullptr, nullptr};
-
+  uint64_t* d_digest = nullptr;
+  SegImage image;
   // diagnostics: MTE_WAVE_CLOCK=<file> dumps pass-1 start / end times per
   // pair (s_memrealtime, 100 MHz) at every mte_sync
   unsigned long long* d_wclock = nullptr;
-  double last_ms = 0, last_ops = 0;  // previous run (pass-1 schedule estimate)
-  const char* wclock_path = nullptr;
-
-  // chunked big-document pass (seg_capacity >= kChunkMinCap, mte_chunk.h)
+  // chunked big-document pass (seg_capacity >= kChunkMinCap, mte_chunk.h) and
+  // its round phases (mte_round.h)
   bool chunked = false;
   ChunkArgs ch{};
-  uint64_t* d_digest = nullptr;
+  RoundArgs rd{};
   // tile-parallel digest of big-document contexts (dg_*_kernel), allocated at
   // the first digest of such a context
   void* d_dgt = nullptr;
   DigestTiles dgt{};
-
-  // text arena
-  uint16_t* arena = nullptr;
-  uint64_t arena_n = 0, arena_cap = 0;
-  std::vector<uint16_t> h_arena;
-  std::vector<mte_propset> h_load_ps;  // mte_load_docs propsets (for mte_load_segments)
-  std::vector<mte_prop> h_load_pe;
-
-  // batch
-  // Two batch slots: mte_submit fills one (validation, pinned staging, DMA on
-  // up_stream) while a replay of the other may still run on `stream`; a slot is
-  // rewritten only after the last run that read it (slot_ev).  mte_run replays
-  // the slot last submitted (rslot).
-  hipStream_t up_stream = nullptr;
-  int rslot = 0;
-  hipEvent_t slot_ev[2] = {nullptr, nullptr};
-  mte_op* d_ops_s[2] = {nullptr, nullptr};
-  uint64_t ops_cap_s[2] = {0, 0};
-  uint4* d_cps_s[2] = {nullptr, nullptr};  // compiled propsets, 2 x uint4 each (props_kernel)
-  uint64_t cps_cap_s[2] = {0, 0};
-  uint64_t* d_off_s[2] = {nullptr, nullptr};
-  uint64_t off_cap_s[2] = {0, 0};
-  mte_propset* d_ps_s[2] = {nullptr, nullptr};
-  uint64_t ps_cap_s[2] = {0, 0};
-  mte_prop* d_pe_s[2] = {nullptr, nullptr};
-  uint64_t pe_cap_s[2] = {0, 0};
-  uint64_t n_ops_s[2] = {0, 0}, n_propsets_s[2] = {0, 0};
-  uint32_t text_base_s[2] = {0, 0};
-  uint64_t max_doc_ops_s[2] = {0, 0};  // the batch's largest per-document op count
-  // the batch mte_run replays (= slot rslot)
-  mte_op* d_ops = nullptr;
-  uint4* d_cps = nullptr;
-  uint64_t n_ops = 0, n_propsets = 0;
   uint32_t* d_pairs = nullptr;  // pass-1 doc pairs (new length calc documents)
   uint32_t n_pairs = 0;         // pass-1 waves
   uint32_t pass1_group = 1;     // documents per pass-1 wave
@@ -616,39 +614,68 @@ struct mte_ctx {
   int32_t* d_hscr = nullptr;        // L / P scratch, 2 x cap per document
   uint32_t* d_htree_docs = nullptr; // the candidates
   uint32_t n_htree = 0;
-  std::vector<uint8_t> h_legacy;    // per doc
+  std::vector<uint32_t> h_htree_docs;
+  std::vector<uint8_t> h_legacy;    // per doc: it carries tree words
   std::vector<uint8_t> h_local;     // per doc: 1 MTE_DOC_LOCAL_CLIENT, 2 MTE_DOC_TREE (the HBM tree pass's)
   std::vector<uint8_t> h_events;    // per doc: MTE_DOC_EVENTS
-  // delta events per batch slot: region offsets (n_docs + 1, host and device),
-  // the events, their counts; ev_slot = the slot of the last mte_run
-  uint32_t ev_per_op = 8;
-  std::vector<uint64_t> h_dl_off_s[2];
-  uint64_t* d_dl_off_s[2] = {nullptr, nullptr};
-  uint64_t dl_off_cap_s[2] = {0, 0};
-  mte_delta* d_dl_s[2] = {nullptr, nullptr};
-  uint64_t dl_cap_s[2] = {0, 0};
-  uint32_t* d_dl_n_s[2] = {nullptr, nullptr};
-  uint64_t dl_n_cap_s[2] = {0, 0};
-  // the streamed pass's document order (longest batch first, so the longest
-  // chains start first): the local-client / event documents by this batch's op
-  // count, then the rest; empty without such documents
+  // the flat HBM-streamed pass's own documents (new length calc with delta
+  // events, no local client): BatchSlot::sorder
   std::vector<uint32_t> h_sdocs;
-  uint32_t* d_sorder_s[2] = {nullptr, nullptr};
-  uint64_t sorder_cap_s[2] = {0, 0};
-  // per batch slot: the documents with MTE_OP_RELPOS records (upload_ops)
-  std::vector<uint32_t> h_rel_s[2];
-  uint32_t* d_rel_s[2] = {nullptr, nullptr};
-  uint64_t rel_cap_s[2] = {0, 0};
-  int ev_slot = -1;
   // local references of the MTE_DOC_REFS documents (mte_stream.h): ref_cap slots
   // per document, zeroed at every reset
   std::vector<uint8_t> h_refs;      // per doc: MTE_DOC_REFS
   std::vector<uint8_t> h_slides;    // per doc: MTE_DOC_SLIDE_EVENTS (with REFS and EVENTS)
-  bool any_maint = false;           // a document records maintenance (the HBM tree pass's M build)
   std::vector<uint32_t> h_ref_hi;   // per doc: reference slots its MTE_OP_REF records used so far (+1)
-  uint32_t ref_cap = 1024;
   uint2* d_refs = nullptr;
+  bool any_maint = false;           // a document records maintenance (the HBM tree pass's M build)
   uint32_t* d_rs_docs = nullptr;    // legacy documents declared MTE_DOC_ROUND_SYNC (flat)
+  uint32_t n_rs = 0;
+};
+
+}  // namespace
+
+struct mte_ctx {
+  int device = 0;
+  uint32_t n_keys = 0, kt = 0;  // kt: template planes (0/4/8)
+  uint32_t cap = 1024;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // the tree pass runs on its own stream beside the flat passes (disjoint
+  // documents), forked after the batch set-up and joined before the read-outs
+  hipStream_t tree_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool ran = false, submitted = false;
+  bool stats_on = true;
+  std::string err;
+
+  DocState docs;              // the loaded documents
+  uint64_t* d_pow = nullptr;  // pow1[32], pow2[32]
+
+  // pinned staging for op-record uploads (mte_submit), allocated on first use
+  static constexpr int kStages = 3;
+  static constexpr size_t kStageBytes = 64ull << 20;
+  void* stage[kStages] = {nullptr, nullptr, nullptr};
+  hipEvent_t stage_ev[kStages] = {nullptr, nullptr, nullptr};
+
+  double last_ms = 0, last_ops = 0;  // previous run (pass-1 schedule estimate); kept across loads
+  const char* wclock_path = nullptr;  // MTE_WAVE_CLOCK (DocState::d_wclock)
+
+  // text arena: restarts with each load's text, keeps its capacity
+  DevBuf<uint16_t> arena;
+  uint64_t arena_n = 0;
+  std::vector<uint16_t> h_arena;
+  std::vector<mte_propset> h_load_ps;  // mte_load_docs propsets (for mte_load_segments)
+  std::vector<mte_prop> h_load_pe;
+
+  // the batch slots; mte_run replays the slot last submitted (rslot), the
+  // read-outs of delta events take the slot of the last mte_run (ev_slot, -1:
+  // no batch with events ran since the load)
+  hipStream_t up_stream = nullptr;
+  BatchSlot slot[2];
+  int rslot = 0;
+  int ev_slot = -1;
+  uint32_t ev_per_op = 8;
+  uint32_t ref_cap = 1024;
   int tree_rounds = 0;              // TIER 0 / TIER 1 rounds (MTE_TREE_ROUNDS; 0 = from the batch)
   // node level (mte_comm_*): the RCCL communicator and its staging buffers
   // the communicator is shared by reference count (mte_comm_share): the last
@@ -656,30 +683,20 @@ struct mte_ctx {
   CommRef* cref = nullptr;
   ncclComm_t comm = nullptr;  // cref->comm, or null
   int world = 1, rank = 0;
-  uint64_t* d_comm = nullptr;  // digests of all ranks / scalar reductions
-  uint64_t comm_cap = 0;       // uint64 elements
-  uint32_t n_rs = 0;
+  DevBuf<uint64_t> d_comm;  // digests of all ranks / scalar reductions (sized exactly, comm_staging)
   // per key, the largest property value id the context was given (load +
   // every batch) and whether any text segment or annotate ever carried it:
   // pass 1 packs the 4 property planes into one (kPack4) when every key's ids
   // fit a byte, or all but a side key that only marker inserts ever set
-  // (ReplayArgs::side_key, config 3's markerId); sticky per context
+  // (ReplayArgs::side_key, config 3's markerId); restart at each load;
+  // MTE_PACK_PROPS=0 turns the packing off
   uint32_t max_vid_k[MTE_MAX_KEYS] = {};
   uint8_t key_text[MTE_MAX_KEYS] = {};
   std::vector<uint8_t> h_text_ps;  // the batch's propsets a text insert or an annotate used
-  // the largest property value id the context was given (load + every batch):
-  // below 256 pass 1 packs the 4 property planes into one (kPack4);
-  // MTE_PACK_PROPS=0 turns that off
-  uint32_t max_vid = 0;
+  std::vector<uint32_t> h_hord;    // mte_submit's staging of BatchSlot::hord (alive until its copy is done)
   bool pack_props = true;
-  // round phases of the chunked pass (mte_round.h); MTE_ROUND_PHASES=0 turns them off
-  RoundArgs rd{};
-  bool round_phases = true;
+  bool round_phases = true;  // round phases of the chunked pass (mte_round.h); MTE_ROUND_PHASES=0 turns them off
   uint32_t htree_lds = 0;  // LDS bytes a document of the HBM tree pass may hold (MTE_HTREE_LDS)
-  std::vector<uint32_t> h_htree_docs, h_hord;
-  uint32_t* d_hord_s[2] = {nullptr, nullptr};  // per batch slot: the candidates, most records first
-  uint64_t hord_cap_s[2] = {0, 0};
-  bool hord_ok_s[2] = {false, false};  // the slot's order is of the loaded documents
   // MTE_HTREE_PROF=<file>: the HBM tree pass's phase clocks (a `make prof`
   // build) appended to <file> at each mte_stats_get
   const char* hprof_path = nullptr;
@@ -694,10 +711,6 @@ struct mte_ctx {
   std::function<int()> tail_fn;
   int tail_rc = 0;
   int tail_slot = -1;  // the batch slot the running tail replays
-  uint64_t* d_off = nullptr;
-  mte_propset* d_ps = nullptr;
-  mte_prop* d_pe = nullptr;
-  uint32_t batch_text_base = 0;
 };
 
 namespace {
@@ -748,14 +761,14 @@ ncclResult_t comm_release(mte_ctx* c) {
   } while (0)
 
 template <typename T>
-int grow(mte_ctx* c, T** p, uint64_t* cap, uint64_t need, bool keep = false, uint64_t keep_n = 0) {
-  if (need <= *cap && *p) return MTE_OK;
-  uint64_t nc = *cap ? *cap : 256;
+int grow(mte_ctx* c, DevBuf<T>& b, uint64_t need, bool keep = false, uint64_t keep_n = 0) {
+  if (need <= b.cap && b.p) return MTE_OK;
+  uint64_t nc = b.cap ? b.cap : 256;
   while (nc < need) nc *= 2;
   T* q = nullptr;
   HIPCHK(c, hipMalloc((void**)&q, nc * sizeof(T)));
-  if (keep && *p && keep_n) HIPCHK(c, hipMemcpyAsync(q, *p, keep_n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  if (*p) {
+  if (keep && b.p && keep_n) HIPCHK(c, hipMemcpyAsync(q, b.p, keep_n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+  if (b.p) {
     // every kernel that may still read the old buffer has to be done: the
     // round phases' tail thread (mte_ctx::tail) enqueues onto the engine
     // stream after this call could sync it, and the tree passes run on their
@@ -765,87 +778,54 @@ int grow(mte_ctx* c, T** p, uint64_t* cap, uint64_t need, bool keep = false, uin
     if (c->tail.joinable()) c->tail.join();
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->tree_stream) HIPCHK(c, hipStreamSynchronize(c->tree_stream));
-    HIPCHK(c, hipFree(*p));
+    HIPCHK(c, hipFree(b.p));
   }
-  *p = q;
-  *cap = nc;
+  b.p = q;
+  b.cap = nc;
   return MTE_OK;
 }
 
 void free_image(mte_ctx* c) {
-  void* ps[] = {c->d_img, c->d_img_doc, c->d_img_off};
+  SegImage& im = c->docs.image;
+  void* ps[] = {im.img, im.doc, im.off};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  c->d_img = nullptr;
-  c->d_img_doc = nullptr;
-  c->d_img_off = nullptr;
-  c->n_img = 0;
+  im = SegImage{};
 }
 
+// Drop everything of the loaded documents.  The batch slots keep their
+// buffers; their order of the HBM tree pass's documents is of this load.
 void free_docs(mte_ctx* c) {
   free_image(c);
-  void* cs[] = {c->ch.arena, c->ch.cnt, c->ch.kc, c->ch.sum, c->rd.plan, c->rd.acct, c->rd.rcnt, c->rd.rbuf, c->rd.rflag,
-                c->rd.nch, c->rd.nnew, c->rd.count, c->rd.rchain, c->rd.live, c->rd.gfl, c->rd.rrec};
-  for (void* p : cs)
-    if (p) (void)hipFree(p);
-  c->ch = ChunkArgs{};
-  c->rd = RoundArgs{};
-  c->chunked = false;
-  if (c->d_wclock) (void)hipFree(c->d_wclock);
-  c->d_wclock = nullptr;
-  if (c->d_dgt) (void)hipFree(c->d_dgt);
-  c->d_dgt = nullptr;
-  c->dgt = DigestTiles{};
-  void* ps[] = {c->hdr, c->soa.len, c->stats, c->d_inits, c->d_init_props, c->d_digest, c->d_pairs,
-                c->d_tree, c->d_heap, c->d_tree_docs, c->d_rs_docs, c->d_refs, c->d_hheap, c->d_hst, c->d_hscr,
-                c->d_htree_docs};
+  DocState& d = c->docs;
+  void* ps[] = {d.hdr, d.soa.len, d.stats, d.d_inits, d.d_init_props, d.d_digest, d.d_wclock, d.d_dgt, d.d_pairs,
+                d.d_tree, d.d_heap, d.d_tree_docs, d.d_hheap, d.d_hst, d.d_hscr, d.d_htree_docs, d.d_refs, d.d_rs_docs,
+                d.ch.arena, d.ch.cnt, d.ch.kc, d.ch.sum, d.rd.plan, d.rd.acct, d.rd.rcnt, d.rd.rbuf, d.rd.rflag,
+                d.rd.nch, d.rd.nnew, d.rd.count, d.rd.rchain, d.rd.live, d.rd.gfl, d.rd.rrec};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  c->d_refs = nullptr;
-  c->d_rs_docs = nullptr;
-  c->n_rs = 0;
-  c->d_tree = nullptr;
-  c->d_heap = nullptr;
-  c->d_tree_docs = nullptr;
-  c->n_tree = 0;
-  c->d_hheap = nullptr;
-  c->d_hst = nullptr;
-  c->d_hscr = nullptr;
-  c->d_htree_docs = nullptr;
-  c->n_htree = 0;
-  c->h_htree_docs.clear();
-  c->hord_ok_s[0] = c->hord_ok_s[1] = false;
-  c->hdr = nullptr;
-  c->soa = SegSoA{};
-  c->stats = nullptr;
-  c->d_inits = nullptr;
-  c->d_init_props = nullptr;
-  c->d_digest = nullptr;
-  c->d_pairs = nullptr;
-  c->n_pairs = 0;
-  c->n_docs = 0;
-  c->rounds_carried = false;
+  d = DocState{};
+  for (BatchSlot& s : c->slot) s.hord_ok = false;
 }
 
 int launch_reset(mte_ctx* c) {
-  if (!c->n_docs) return MTE_OK;
-  const uint32_t blocks = (c->n_docs + 255) / 256;
-  hipLaunchKernelGGL(reset_kernel, dim3(blocks), dim3(256), 0, c->stream, c->hdr, c->soa, c->cap,
-                     c->d_inits, c->d_init_props, c->n_keys, c->n_docs, (const uint64_t*)c->d_img_off, c->d_tree,
-                     c->kt, c->d_hst);
+  DocState& d = c->docs;
+  if (!d.n_docs) return MTE_OK;
+  const uint32_t blocks = (d.n_docs + 255) / 256;
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks), dim3(256), 0, c->stream, d.hdr, d.soa, c->cap, d.d_inits,
+                     d.d_init_props, c->n_keys, d.n_docs, (const uint64_t*)d.image.off, d.d_tree, c->kt, d.d_hst);
   HIPCHK(c, hipGetLastError());
-  if (c->d_refs)
-    HIPCHK(c, hipMemsetAsync(c->d_refs, 0, sizeof(uint2) * (size_t)c->ref_cap * c->n_docs, c->stream));
-  std::fill(c->h_ref_hi.begin(), c->h_ref_hi.end(), 0u);  // the references are gone
-  if (c->n_img) {
-    const uint64_t nb = std::min<uint64_t>((c->n_img + 255) / 256, 65536);
-    hipLaunchKernelGGL(image_kernel, dim3((uint32_t)nb), dim3(256), 0, c->stream, c->soa, c->cap,
-                       (uint32_t)(kFieldPlanes + c->kt), c->d_img, c->n_img, c->d_img_doc,
-                       (const uint64_t*)c->d_img_off, c->n_img, c->d_tree, c->img_uc);
+  if (d.d_refs) HIPCHK(c, hipMemsetAsync(d.d_refs, 0, sizeof(uint2) * (size_t)c->ref_cap * d.n_docs, c->stream));
+  std::fill(d.h_ref_hi.begin(), d.h_ref_hi.end(), 0u);  // the references are gone
+  if (d.image.n) {
+    const uint64_t nb = std::min<uint64_t>((d.image.n + 255) / 256, 65536);
+    hipLaunchKernelGGL(image_kernel, dim3((uint32_t)nb), dim3(256), 0, c->stream, d.soa, c->cap,
+                       (uint32_t)(kFieldPlanes + c->kt), d.image.img, d.image.n, d.image.doc,
+                       (const uint64_t*)d.image.off, d.image.n, d.d_tree, d.image.uc);
     HIPCHK(c, hipGetLastError());
   }
   c->ran = false;
-  c->rounds_carried = false;
+  d.rounds_carried = false;
   return MTE_OK;
 }
 
@@ -855,23 +835,23 @@ int launch_reset(mte_ctx* c) {
 template <int K>
 int round_phase_loop(mte_ctx* c, const ReplayArgs& a, size_t lds) {
   HIPCHK(c, hipSetDevice(c->device));
-  ChunkArgs ch = c->ch;
-  RoundArgs rd = c->rd;
+  ChunkArgs ch = c->docs.ch;
+  RoundArgs rd = c->docs.rd;
   ch.plan = rd.plan;
   ch.rflag = rd.rflag;
   rd.planes = kFieldPlanes + (uint32_t)(K > 0 ? K : 0);
-  HIPCHK(c, hipMemsetAsync(rd.acct, 0, sizeof(unsigned long long) * c->n_docs, c->stream));
+  HIPCHK(c, hipMemsetAsync(rd.acct, 0, sizeof(unsigned long long) * c->docs.n_docs, c->stream));
   // no document starts in the arena (rd.live: a run's chunks stay laid out for
   // the document's next run and go back to the flat planes when it leaves)
-  HIPCHK(c, hipMemsetAsync(rd.live, 0, 4 * (uint64_t)c->n_docs, c->stream));
+  HIPCHK(c, hipMemsetAsync(rd.live, 0, 4 * (uint64_t)c->docs.n_docs, c->stream));
   rd.d0 = 0;
-  rd.nd = c->n_docs;
+  rd.nd = c->docs.n_docs;
   bool carried = false;  // some document may be in the arena
-  const uint64_t nch_all = (uint64_t)c->n_docs * ch.nch_cap;
+  const uint64_t nch_all = (uint64_t)c->docs.n_docs * ch.nch_cap;
   for (int ph = 0; ph < kMaxPhases; ph++) {
     rd.last = ph == kMaxPhases - 1 ? 1u : 0u;
     HIPCHK(c, hipMemsetAsync(rd.count, 0, 16, c->stream));
-    HIPCHK(c, launch_round_plan(a, ch, rd, c->n_docs, c->stream));
+    HIPCHK(c, launch_round_plan(a, ch, rd, c->docs.n_docs, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_rcount, rd.count, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint32_t n_round = c->h_rcount[0], n_active = c->h_rcount[2];
@@ -881,14 +861,14 @@ int round_phase_loop(mte_ctx* c, const ReplayArgs& a, size_t lds) {
       const uint32_t want = c->h_rcount[3] < 64u ? 64u : c->h_rcount[3];
       rd.col_cap = (want + 63u) / 64u * 64u;
       HIPCHK(c, hipMemsetAsync(rd.rcnt, 0, nch_all * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(rd.rflag, 0, 4 * (uint64_t)c->n_docs, c->stream));
-      HIPCHK(c, (launch_round_run<K>(a, ch, rd, c->n_docs, c->stream)));
+      HIPCHK(c, hipMemsetAsync(rd.rflag, 0, 4 * (uint64_t)c->docs.n_docs, c->stream));
+      HIPCHK(c, (launch_round_run<K>(a, ch, rd, c->docs.n_docs, c->stream)));
       carried = true;
-      c->rounds_carried = true;
+      c->docs.rounds_carried = true;
     } else if (carried) {  // the carried documents' runs are not rounds: back to the flat planes
       HIPCHK(c, (launch_round_gather<K>(a, ch, rd, 0, c->stream)));
     }
-    HIPCHK(c, (launch_chunk<K, false>(a, ch, c->n_docs, lds, c->stream)));
+    HIPCHK(c, (launch_chunk<K, false>(a, ch, c->docs.n_docs, lds, c->stream)));
   }
   if (carried) HIPCHK(c, (launch_round_gather<K>(a, ch, rd, 1, c->stream)));
   return MTE_OK;
@@ -896,11 +876,12 @@ int round_phase_loop(mte_ctx* c, const ReplayArgs& a, size_t lds) {
 
 template <int K, bool S>
 int launch_replay(mte_ctx* c, const ReplayArgs& a) {
+  const BatchSlot& sl = c->slot[c->rslot];
   // the tree pass: legacy length calc documents (mte_tree.h), up to 252
   // items at E <= 4, then up to 1,020 at E = 8 / 16; then the HBM tree pass
   // (mte_htree.h): the legacy documents past that and every document with a
   // local client
-  if (c->n_tree || c->n_htree) {
+  if (c->docs.n_tree || c->docs.n_htree) {
     if (!c->tree_stream) {
       HIPCHK(c, hipStreamCreateWithFlags(&c->tree_stream, hipStreamNonBlocking));
       HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -910,33 +891,34 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
     // tree document), so the two streams share no document state
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->tree_stream, c->ev_fork, 0));
-    if (c->n_tree) {
-      TreeArgs t{c->d_tree, c->d_heap, c->d_tree_docs, c->n_tree, c->arena, 0u, 0u};
+    if (c->docs.n_tree) {
+      TreeArgs t{c->docs.d_tree, c->docs.d_heap, c->docs.d_tree_docs, c->docs.n_tree, c->arena.p, 0u, 0u};
       // rounds of at most ~625 ops per document (MTE_TREE_ROUNDS overrides the count)
-      const uint64_t mx = c->max_doc_ops_s[c->rslot];
+      const uint64_t mx = sl.max_doc_ops;
       int rounds = c->tree_rounds > 0 ? c->tree_rounds : (int)std::min<uint64_t>(32, std::max<uint64_t>(1, (mx + 624) / 625));
       const uint32_t per = (uint32_t)((mx + (uint64_t)rounds - 1) / (uint64_t)rounds);
-      HIPCHK(c, (launch_tree<K, S>(a, t, (c->n_tree + kDocsPerBlock - 1) / kDocsPerBlock, c->tree_stream, rounds,
+      HIPCHK(c, (launch_tree<K, S>(a, t, (c->docs.n_tree + kDocsPerBlock - 1) / kDocsPerBlock, c->tree_stream, rounds,
                                    per ? per : 1u)));
     }
-    if (c->n_htree) {
+    if (c->docs.n_htree) {
       // LDS residency: (nP + 5) words per item (mte_htree.h ht_to_lds), whole wavefronts' worth
       const uint32_t words = (uint32_t)(kLocalPlanes<K> + 5);
       uint32_t lcap = c->htree_lds >= 8 ? (c->htree_lds / 4 - 2) / words / kWave * kWave : 0u;
       if (lcap > c->cap) lcap = c->cap / kWave * kWave;
-      const uint32_t* order = c->hord_ok_s[c->rslot] ? c->d_hord_s[c->rslot] : c->d_htree_docs;
+      const uint32_t* order = sl.hord_ok ? sl.hord.p : c->docs.d_htree_docs;
       if (c->hprof_path && !c->d_hprof) {
         HIPCHK(c, hipMalloc((void**)&c->d_hprof, kHtProf * 8));
         HIPCHK(c, hipMemsetAsync(c->d_hprof, 0, kHtProf * 8, c->tree_stream));
       }
-      HtreeArgs ht{c->d_tree, c->d_heap, c->d_hheap, c->hcap, lcap, c->d_hst, c->d_hscr, order, c->n_htree,
-                   c->arena, c->d_hprof, c->any_maint ? 1u : 0u};
+      const DocState& d = c->docs;
+      HtreeArgs ht{d.d_tree, d.d_heap, d.d_hheap, d.hcap, lcap, d.d_hst, d.d_hscr, order, d.n_htree,
+                   c->arena.p, c->d_hprof, c->docs.any_maint ? 1u : 0u};
       HIPCHK(c, (launch_htree<K, S>(a, ht, c->tree_stream)));
     }
     HIPCHK(c, hipEventRecord(c->ev_join, c->tree_stream));
   }
   // pass 1: two documents per wavefront (docs up to 126 segments)
-  const uint32_t b1 = (c->n_pairs + kPairsPerBlock - 1) / kPairsPerBlock;
+  const uint32_t b1 = (c->docs.n_pairs + kPairsPerBlock - 1) / kPairsPerBlock;
   // with 4 keys whose value ids all fit in a byte (every value the context was
   // ever given), pass 1 holds the four planes as one packed register plane
   if (b1) {
@@ -958,13 +940,13 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
     }
   }
   // pass 2: docs that outgrew pass 1 continue one per wavefront (up to 1022 segments)
-  const uint32_t b2 = (c->n_docs + kDocsPerBlock - 1) / kDocsPerBlock;
+  const uint32_t b2 = (c->docs.n_docs + kDocsPerBlock - 1) / kDocsPerBlock;
   HIPCHK(c, (launch_big<K, S>(a, b2, c->stream)));
   // pass 3: larger docs (up to the ctx capacity): the chunked pass in big-doc
   // contexts, otherwise HBM-resident and streamed per op
-  if (c->chunked) {
-    const size_t lds = sizeof(uint32_t) * MTE_MAX_CLIENTS * c->ch.ng_cap + sizeof(ChCtl);
-    const uint64_t col_bytes = rnd_resolve_lds(c->ch.nch_cap, c->ch.ng_cap);
+  if (c->docs.chunked) {
+    const size_t lds = sizeof(uint32_t) * MTE_MAX_CLIENTS * c->docs.ch.ng_cap + sizeof(ChCtl);
+    const uint64_t col_bytes = rnd_resolve_lds(c->docs.ch.nch_cap, c->docs.ch.ng_cap);
     if (!S && c->round_phases && col_bytes <= kRoundLdsMax) {
       // round phases (mte_round.h): each phase plans every escalated
       // document's next run, replays the round-shaped runs chunk-parallel and
@@ -973,7 +955,7 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
       c->tail_fn = [c, a, lds]() -> int { return round_phase_loop<K>(c, a, lds); };
       return MTE_OK;  // the tail joins the tree stream after the loop
     } else {
-      HIPCHK(c, (launch_chunk<K, S>(a, c->ch, c->n_docs, lds, c->stream)));
+      HIPCHK(c, (launch_chunk<K, S>(a, c->docs.ch, c->docs.n_docs, lds, c->stream)));
     }
   } else {
     HIPCHK(c, (launch_stream<K, S>(a, b2, c->stream)));
@@ -1085,8 +1067,9 @@ int upload_ops(mte_ctx* c, const mte_batch* b, int w, uint64_t* bad, const char*
         for (uint64_t k = a; k < e; k++) {
           while (d + 1 < b->n_docs && b->op_offsets[d + 1] <= k0 + k) d++;
           const mte_op& o = b->ops[k0 + k];
-          const uint8_t hl = c->h_local.empty() ? 0 : c->h_local[d];
-          const char* r = bad_op(o, b, (hl & 1) != 0, (hl & 2) != 0, !c->h_refs.empty() && c->h_refs[d], c->ref_cap);
+          const uint8_t hl = c->docs.h_local.empty() ? 0 : c->docs.h_local[d];
+          const bool refs = !c->docs.h_refs.empty() && c->docs.h_refs[d];
+          const char* r = bad_op(o, b, (hl & 1) != 0, (hl & 2) != 0, refs, c->ref_cap);
           if (!r && o.type == MTE_OP_RELPOS) {
             const mte_op* nx = k0 + k + 1 < b->op_offsets[d + 1] ? &b->ops[k0 + k + 1] : nullptr;
             if (!nx || nx->type > MTE_OP_ANNOTATE) r = "relative position record not followed by an insert, remove "
@@ -1124,7 +1107,7 @@ int upload_ops(mte_ctx* c, const mte_batch* b, int w, uint64_t* bad, const char*
     }
     for (auto& t : th) t.join();
     if (first_bad.load() != UINT64_MAX) break;
-    HIPCHK(c, hipMemcpyAsync(c->d_ops_s[w] + k0, dst, n * sizeof(mte_op), hipMemcpyHostToDevice, c->up_stream));
+    HIPCHK(c, hipMemcpyAsync(c->slot[w].ops.p + k0, dst, n * sizeof(mte_op), hipMemcpyHostToDevice, c->up_stream));
     HIPCHK(c, hipEventRecord(c->stage_ev[si], c->up_stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->up_stream));
@@ -1138,7 +1121,7 @@ int upload_ops(mte_ctx* c, const mte_batch* b, int w, uint64_t* bad, const char*
   c->h_text_ps.assign(b->n_propsets, 0);
   for (const auto& v : tps)
     for (uint32_t i = 0; i < b->n_propsets; i++) c->h_text_ps[i] |= v[i];
-  std::vector<uint32_t>& rd = c->h_rel_s[w];
+  std::vector<uint32_t>& rd = c->slot[w].h_rel;
   rd.clear();
   for (const auto& v : rels) rd.insert(rd.end(), v.begin(), v.end());
   std::sort(rd.begin(), rd.end());
@@ -1222,16 +1205,10 @@ int mte_destroy(mte_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   free_docs(c);
-  void* ps[] = {c->arena, c->d_pow, c->d_hprof};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  for (int w = 0; w < 2; w++) {
-    void* sl[] = {c->d_ops_s[w], c->d_cps_s[w], c->d_off_s[w], c->d_ps_s[w], c->d_pe_s[w],
-                  c->d_dl_off_s[w], c->d_dl_s[w], c->d_dl_n_s[w], c->d_sorder_s[w], c->d_rel_s[w], c->d_hord_s[w]};
-    for (void* p : sl)
-      if (p) (void)hipFree(p);
-    if (c->slot_ev[w]) (void)hipEventDestroy(c->slot_ev[w]);
-  }
+  free_buf(c->arena);
+  if (c->d_pow) (void)hipFree(c->d_pow);
+  if (c->d_hprof) (void)hipFree(c->d_hprof);
+  for (BatchSlot& s : c->slot) s.release();
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
   for (int i = 0; i < mte_ctx::kStages; i++) {
     if (c->stage[i]) (void)hipHostFree(c->stage[i]);
@@ -1239,7 +1216,7 @@ int mte_destroy(mte_ctx* c) {
   }
   comm_release(c);
   if (c->h_rcount) (void)hipHostFree(c->h_rcount);
-  if (c->d_comm) (void)hipFree(c->d_comm);
+  free_buf(c->d_comm);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->tree_stream) (void)hipStreamDestroy(c->tree_stream);
@@ -1292,10 +1269,8 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
     }
   }
   free_docs(c);
-  c->n_docs = n_docs;
+  c->docs.n_docs = n_docs;
   c->submitted = false;
-  c->max_vid = 0;
-  for (uint32_t i = 0; props && i < n_props; i++) c->max_vid = std::max(c->max_vid, props[i].value);
   for (uint32_t k = 0; k < MTE_MAX_KEYS; k++) c->max_vid_k[k] = 0, c->key_text[k] = 0;
   for (uint32_t i = 0; props && i < n_props; i++)
     if (props[i].key < MTE_MAX_KEYS) c->max_vid_k[props[i].key] = std::max(c->max_vid_k[props[i].key], props[i].value);
@@ -1305,33 +1280,31 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
       for (uint32_t t = 0; t < ps.count; t++)
         if (props[ps.first + t].key < MTE_MAX_KEYS) c->key_text[props[ps.first + t].key] = 1;
     }
-  c->ev_slot = -1;
-  c->n_ops = 0;
+  c->ev_slot = -1;  // nothing of an earlier batch is reachable until the next mte_submit
+  for (BatchSlot& s : c->slot) s.n_ops = 0;
   const uint64_t nslots = (uint64_t)(n_docs ? n_docs : 1) * c->cap;
-  c->soa.plane_stride = nslots;
-  c->h_local.assign(n_docs, 0);
-  c->h_events.assign(n_docs, 0);
-  c->h_refs.assign(n_docs, 0);
-  c->h_slides.assign(n_docs, 0);
-  c->any_maint = false;
+  c->docs.soa.plane_stride = nslots;
+  c->docs.h_local.assign(n_docs, 0);
+  c->docs.h_events.assign(n_docs, 0);
+  c->docs.h_refs.assign(n_docs, 0);
+  c->docs.h_slides.assign(n_docs, 0);
   for (uint32_t d = 0; d < n_docs; d++)
-    if (docs[d].flags & MTE_DOC_MAINT_EVENTS) c->any_maint = true;
-  c->h_ref_hi.assign(n_docs, 0);
+    if (docs[d].flags & MTE_DOC_MAINT_EVENTS) c->docs.any_maint = true;
+  c->docs.h_ref_hi.assign(n_docs, 0);
   bool any_local = false, any_refs = false;
-  c->h_sdocs.clear();
   for (uint32_t d = 0; d < n_docs; d++) {
     // the flat HBM-streamed pass's own: new length-calc documents with delta events and no local client
     if ((docs[d].flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_TREE)) ==
         (MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC))
-      c->h_sdocs.push_back(d);
-    if (docs[d].flags & MTE_DOC_LOCAL_CLIENT) c->h_local[d] = 1, any_local = true;
-    else if (docs[d].flags & MTE_DOC_TREE) c->h_local[d] = 2, any_local = true;
-    if (docs[d].flags & MTE_DOC_EVENTS) c->h_events[d] = 1;
-    if (docs[d].flags & MTE_DOC_REFS) c->h_refs[d] = 1, any_refs = true;
+      c->docs.h_sdocs.push_back(d);
+    if (docs[d].flags & MTE_DOC_LOCAL_CLIENT) c->docs.h_local[d] = 1, any_local = true;
+    else if (docs[d].flags & MTE_DOC_TREE) c->docs.h_local[d] = 2, any_local = true;
+    if (docs[d].flags & MTE_DOC_EVENTS) c->docs.h_events[d] = 1;
+    if (docs[d].flags & MTE_DOC_REFS) c->docs.h_refs[d] = 1, any_refs = true;
     const uint32_t sl = MTE_DOC_REFS | MTE_DOC_EVENTS | MTE_DOC_SLIDE_EVENTS;
-    if ((docs[d].flags & sl) == sl) c->h_slides[d] = 1;
+    if ((docs[d].flags & sl) == sl) c->docs.h_slides[d] = 1;
   }
-  if (any_refs) HIPCHK(c, hipMalloc((void**)&c->d_refs, sizeof(uint2) * (size_t)c->ref_cap * n_docs));
+  if (any_refs) HIPCHK(c, hipMalloc((void**)&c->docs.d_refs, sizeof(uint2) * (size_t)c->ref_cap * n_docs));
   // documents with a local client hold 2 kt + 6 more planes (mte_htree.h): the
   // pending property keys, the annotate-group mask, the keys' values before
   // their first pending annotate, localRemovedSeq, the removal-group order, the
@@ -1339,28 +1312,28 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
   // group, the removers of short ids 32 .. 63 (the last one MTE_DOC_TREE
   // documents use too)
   const uint64_t prop_planes = (c->kt ? c->kt : 1) + (any_local ? 2 * c->kt + 6 : 0);
-  HIPCHK(c, hipMalloc((void**)&c->hdr, sizeof(DocHdr) * (n_docs ? n_docs : 1)));
+  HIPCHK(c, hipMalloc((void**)&c->docs.hdr, sizeof(DocHdr) * (n_docs ? n_docs : 1)));
   // one allocation, planes at stride nslots: len seq rseq rmask meta toff props[kt]
   // (kt >= n_keys planes, so the register-resident kernels never index past it)
   {
     const uint64_t planes = kFieldPlanes + prop_planes;
     uint32_t* base = nullptr;
     HIPCHK(c, hipMalloc((void**)&base, nslots * 4 * planes));
-    c->soa.len = (int32_t*)base;
-    c->soa.seq = (int32_t*)(base + 1 * nslots);
-    c->soa.rseq = (int32_t*)(base + 2 * nslots);
-    c->soa.rmask = base + 3 * nslots;
-    c->soa.meta = base + 4 * nslots;
-    c->soa.toff = base + 5 * nslots;
-    c->soa.props = base + kFieldPlanes * nslots;
+    c->docs.soa.len = (int32_t*)base;
+    c->docs.soa.seq = (int32_t*)(base + 1 * nslots);
+    c->docs.soa.rseq = (int32_t*)(base + 2 * nslots);
+    c->docs.soa.rmask = base + 3 * nslots;
+    c->docs.soa.meta = base + 4 * nslots;
+    c->docs.soa.toff = base + 5 * nslots;
+    c->docs.soa.props = base + kFieldPlanes * nslots;
   }
-  HIPCHK(c, hipMemsetAsync(c->soa.props, 0, nslots * 4 * prop_planes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->docs.soa.props, 0, nslots * 4 * prop_planes, c->stream));
   if (c->cap >= kChunkMinCap && n_docs) {
     // chunk arena: every doc can be re-laid out at kChFill segments per chunk
     const uint32_t nch_cap = c->cap / kChFill + 2;
     const uint32_t ng_cap = (nch_cap + kChGroup - 1) / kChGroup;
     if (ng_cap <= kChMaxGroups) {
-      ChunkArgs& ch = c->ch;
+      ChunkArgs& ch = c->docs.ch;
       ch.nch_cap = nch_cap;
       ch.ng_cap = ng_cap;
       const uint64_t nch_all = (uint64_t)n_docs * nch_cap;
@@ -1370,7 +1343,7 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
       HIPCHK(c, hipMalloc((void**)&ch.cnt, nch_all * 4));
       HIPCHK(c, hipMalloc((void**)&ch.kc, nch_all * 4));
       HIPCHK(c, hipMalloc((void**)&ch.sum, nch_all * 4 * MTE_MAX_CLIENTS));
-      RoundArgs& rd = c->rd;
+      RoundArgs& rd = c->docs.rd;
       HIPCHK(c, hipMalloc((void**)&rd.plan, sizeof(uint4) * n_docs));
       HIPCHK(c, hipMalloc((void**)&rd.acct, sizeof(unsigned long long) * n_docs));
       HIPCHK(c, hipMemsetAsync(rd.acct, 0, sizeof(unsigned long long) * n_docs, c->stream));
@@ -1385,14 +1358,14 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
       HIPCHK(c, hipMalloc((void**)&rd.gfl, 4 * (uint64_t)n_docs));
       HIPCHK(c, hipMalloc((void**)&rd.count, 16));
       if (!c->h_rcount) HIPCHK(c, hipHostMalloc((void**)&c->h_rcount, 16, 0));
-      c->chunked = true;
+      c->docs.chunked = true;
     }
   }
-  HIPCHK(c, hipMalloc((void**)&c->stats, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1)));
-  HIPCHK(c, hipMemsetAsync(c->stats, 0, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1), c->stream));
-  HIPCHK(c, hipMalloc((void**)&c->d_inits, sizeof(mte_doc_init) * (n_docs ? n_docs : 1)));
-  HIPCHK(c, hipMalloc((void**)&c->d_init_props, sizeof(uint32_t) * iprops.size() + 4));
-  HIPCHK(c, hipMalloc((void**)&c->d_digest, sizeof(uint64_t) * 4 * (n_docs ? n_docs : 1)));
+  HIPCHK(c, hipMalloc((void**)&c->docs.stats, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1)));
+  HIPCHK(c, hipMemsetAsync(c->docs.stats, 0, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1), c->stream));
+  HIPCHK(c, hipMalloc((void**)&c->docs.d_inits, sizeof(mte_doc_init) * (n_docs ? n_docs : 1)));
+  HIPCHK(c, hipMalloc((void**)&c->docs.d_init_props, sizeof(uint32_t) * iprops.size() + 4));
+  HIPCHK(c, hipMalloc((void**)&c->docs.d_digest, sizeof(uint64_t) * 4 * (n_docs ? n_docs : 1)));
   {
     // pass-1 groups: g consecutive documents per wave, g the smallest count
     // that puts the whole batch on the chip at once (CUs x 4 SIMDs x
@@ -1403,12 +1376,12 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
     // Round-synchronous legacy documents (MTE_DOC_ROUND_SYNC) stay flat, behind
     // the per-batch check of round_sync_kernel.
     std::vector<uint32_t> flat_docs, tree_docs, rs_docs, htree_docs;
-    c->h_legacy.assign(n_docs, 0);  // the document carries tree words (read-outs join merged leaves)
+    c->docs.h_legacy.assign(n_docs, 0);  // the document carries tree words (read-outs join merged leaves)
     for (uint32_t d = 0; d < n_docs; d++) {
       const uint32_t f = docs[d].flags;
       if ((f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) || ((f & MTE_DOC_EVENTS) && !(f & MTE_DOC_NEW_LENGTH_CALC))) {
         htree_docs.push_back(d);  // the HBM tree pass's own (mte_htree.h)
-        c->h_legacy[d] = 1;
+        c->docs.h_legacy[d] = 1;
       } else if (f & MTE_DOC_EVENTS) {
         continue;  // the HBM-streamed flat pass replays them (mte_stream.h)
       } else if (docs[d].flags & MTE_DOC_NEW_LENGTH_CALC) {
@@ -1418,7 +1391,7 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
         rs_docs.push_back(d);
       } else {
         tree_docs.push_back(d);
-        c->h_legacy[d] = 1;
+        c->docs.h_legacy[d] = 1;
       }
     }
     const uint32_t nf = (uint32_t)flat_docs.size();
@@ -1426,40 +1399,40 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) n_cu = 0;
     const uint64_t resident = (n_cu > 0 ? (uint64_t)n_cu : 256) * 4 * (uint64_t)pass1_waves();
     const uint32_t g = (uint32_t)std::min<uint64_t>(kGroupMax, std::max<uint64_t>(1, (nf + resident - 1) / resident));
-    c->pass1_group = g;
-    c->n_pairs = (nf + g - 1) / g;
-    std::vector<uint32_t> pairs((size_t)c->n_pairs * g + g, 0xffffffffu);
+    c->docs.pass1_group = g;
+    c->docs.n_pairs = (nf + g - 1) / g;
+    std::vector<uint32_t> pairs((size_t)c->docs.n_pairs * g + g, 0xffffffffu);
     for (uint32_t i = 0; i < nf; i++) pairs[i] = flat_docs[i];
-    HIPCHK(c, hipMalloc((void**)&c->d_pairs, pairs.size() * 4));
-    HIPCHK(c, hipMemcpy(c->d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
-    c->n_rs = (uint32_t)rs_docs.size();
-    if (c->n_rs) {
-      HIPCHK(c, hipMalloc((void**)&c->d_rs_docs, rs_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->d_rs_docs, rs_docs.data(), rs_docs.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc((void**)&c->docs.d_pairs, pairs.size() * 4));
+    HIPCHK(c, hipMemcpy(c->docs.d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
+    c->docs.n_rs = (uint32_t)rs_docs.size();
+    if (c->docs.n_rs) {
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_rs_docs, rs_docs.size() * 4));
+      HIPCHK(c, hipMemcpy(c->docs.d_rs_docs, rs_docs.data(), rs_docs.size() * 4, hipMemcpyHostToDevice));
     }
-    c->n_tree = (uint32_t)tree_docs.size();
-    if (c->n_tree) {
-      HIPCHK(c, hipMalloc((void**)&c->d_heap, sizeof(uint2) * (kTreeHeapCap + 1) * (size_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->d_tree_docs, tree_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->d_tree_docs, tree_docs.data(), tree_docs.size() * 4, hipMemcpyHostToDevice));
+    c->docs.n_tree = (uint32_t)tree_docs.size();
+    if (c->docs.n_tree) {
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_heap, sizeof(uint2) * (kTreeHeapCap + 1) * (size_t)n_docs));
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_tree_docs, tree_docs.size() * 4));
+      HIPCHK(c, hipMemcpy(c->docs.d_tree_docs, tree_docs.data(), tree_docs.size() * 4, hipMemcpyHostToDevice));
     }
     // the HBM tree pass takes its own documents and the legacy ones the
-    // register tiers hand over (past 1,020 items)
-    // (past 1,020 items, or from a batch with relative positions)
+    // register tiers hand over (past 1,020 items, or from a batch with
+    // relative positions)
     for (uint32_t d : tree_docs) htree_docs.push_back(d);
-    c->n_htree = (uint32_t)htree_docs.size();
-    if (c->n_tree || c->n_htree) {
-      HIPCHK(c, hipMalloc((void**)&c->d_tree, nslots * 4));
-      HIPCHK(c, hipMemsetAsync(c->d_tree, 0, nslots * 4, c->stream));
+    c->docs.n_htree = (uint32_t)htree_docs.size();
+    if (c->docs.n_tree || c->docs.n_htree) {
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_tree, nslots * 4));
+      HIPCHK(c, hipMemsetAsync(c->docs.d_tree, 0, nslots * 4, c->stream));
     }
-    if (c->n_htree) {
-      c->hcap = c->cap;  // one heap entry per slot
-      HIPCHK(c, hipMalloc((void**)&c->d_hheap, sizeof(uint2) * ((size_t)c->hcap + 1) * n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->d_hst, sizeof(uint32_t) * kHtState * (size_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->d_hscr, sizeof(int32_t) * 2 * nslots));
-      c->h_htree_docs = htree_docs;
-      HIPCHK(c, hipMalloc((void**)&c->d_htree_docs, htree_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->d_htree_docs, htree_docs.data(), htree_docs.size() * 4, hipMemcpyHostToDevice));
+    if (c->docs.n_htree) {
+      c->docs.hcap = c->cap;  // one heap entry per slot
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_hheap, sizeof(uint2) * ((size_t)c->docs.hcap + 1) * n_docs));
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_hst, sizeof(uint32_t) * kHtState * (size_t)n_docs));
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_hscr, sizeof(int32_t) * 2 * nslots));
+      c->docs.h_htree_docs = htree_docs;
+      HIPCHK(c, hipMalloc((void**)&c->docs.d_htree_docs, htree_docs.size() * 4));
+      HIPCHK(c, hipMemcpy(c->docs.d_htree_docs, htree_docs.data(), htree_docs.size() * 4, hipMemcpyHostToDevice));
     }
   }
   if (n_docs) {
@@ -1472,8 +1445,8 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
           break;
         }
     }
-    HIPCHK(c, hipMemcpy(c->d_inits, dinit.data(), sizeof(mte_doc_init) * n_docs, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpyAsync(c->d_init_props, iprops.data(), sizeof(uint32_t) * iprops.size(),
+    HIPCHK(c, hipMemcpy(c->docs.d_inits, dinit.data(), sizeof(mte_doc_init) * n_docs, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpyAsync(c->docs.d_init_props, iprops.data(), sizeof(uint32_t) * iprops.size(),
                              hipMemcpyHostToDevice, c->stream));
   }
   c->h_load_ps.assign(propsets, propsets + (propsets ? n_propsets : 0));
@@ -1483,10 +1456,10 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
   // text arena restarts with the load text
   c->arena_n = 0;
   c->h_arena.assign(text, text + text_units);
-  int rc = grow(c, &c->arena, &c->arena_cap, text_units + 1);
+  int rc = grow(c, c->arena, text_units + 1);
   if (rc) return rc;
   if (text_units)
-    HIPCHK(c, hipMemcpyAsync(c->arena, text, text_units * 2, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->arena.p, text, text_units * 2, hipMemcpyHostToDevice, c->stream));
   c->arena_n = text_units;
   rc = launch_reset(c);
   if (rc) return rc;
@@ -1497,8 +1470,8 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
 int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* segs, uint64_t n_segs) {
   if (!c || !seg_offsets || (n_segs && !segs)) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (!c->n_docs) return MTE_OK;
-  if (seg_offsets[0] != 0 || seg_offsets[c->n_docs] != n_segs)
+  if (!c->docs.n_docs) return MTE_OK;
+  if (seg_offsets[0] != 0 || seg_offsets[c->docs.n_docs] != n_segs)
     return set_err(c, MTE_E_INVALID_ARG, "seg_offsets must run from 0 to n_segs");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1509,7 +1482,7 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
   // propsets of the load: the load propsets/props were consumed by
   // mte_load_docs; the per-doc initial props are kept, so segment propsets
   // arrive here through the host copy (set by mte_load_docs)
-  for (uint32_t d = 0; d < c->n_docs; d++) {
+  for (uint32_t d = 0; d < c->docs.n_docs; d++) {
     const uint64_t b = seg_offsets[d], e = seg_offsets[d + 1];
     if (e < b || e - b > c->cap) return set_err(c, MTE_E_CAPACITY, "doc %u: %llu segments > capacity %u", d,
                                                 (unsigned long long)(e - b), c->cap);
@@ -1528,7 +1501,7 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
       img[4 * n_segs + g] = (uint32_t)(sg.client + 1) | (sg.kind << 8);
       // a marker of an MTE_DOC_REFS document is named by its index in the load
       // (above every arena offset), as an inserted one by its reserved unit
-      img[5 * n_segs + g] = marker ? (c->h_refs[d] ? 0x80000000u + (uint32_t)(g - b) : 0u) : sg.text_off;
+      img[5 * n_segs + g] = marker ? (c->docs.h_refs[d] ? 0x80000000u + (uint32_t)(g - b) : 0u) : sg.text_off;
       {
         const uint64_t nd = e - b, k = g - b;
         int depth = 1;
@@ -1561,23 +1534,23 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
   if (!n_segs) return launch_reset(c);
   // planes with one value throughout (config 5's preloaded one-unit segments:
   // all but the text offsets and tree words) are not read back at each reset
-  c->img_uc = ImgConst{};
+  c->docs.image.uc = ImgConst{};
   for (uint32_t p = 0; p < np && p < 16; p++) {
     const uint32_t* v = img.data() + (size_t)p * n_segs;
     bool same = true;
     for (uint64_t g = 1; g < n_segs && same; g++) same = v[g] == v[0];
     if (same) {
-      c->img_uc.mask |= 1u << p;
-      c->img_uc.val[p] = v[0];
+      c->docs.image.uc.mask |= 1u << p;
+      c->docs.image.uc.val[p] = v[0];
     }
   }
-  HIPCHK(c, hipMalloc((void**)&c->d_img, img.size() * 4));
-  HIPCHK(c, hipMalloc((void**)&c->d_img_doc, doc.size() * 4));
-  HIPCHK(c, hipMalloc((void**)&c->d_img_off, ((size_t)c->n_docs + 1) * 8));
-  HIPCHK(c, hipMemcpy(c->d_img, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_img_doc, doc.data(), doc.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_img_off, seg_offsets, ((size_t)c->n_docs + 1) * 8, hipMemcpyHostToDevice));
-  c->n_img = n_segs;
+  HIPCHK(c, hipMalloc((void**)&c->docs.image.img, img.size() * 4));
+  HIPCHK(c, hipMalloc((void**)&c->docs.image.doc, doc.size() * 4));
+  HIPCHK(c, hipMalloc((void**)&c->docs.image.off, ((size_t)c->docs.n_docs + 1) * 8));
+  HIPCHK(c, hipMemcpy(c->docs.image.img, img.data(), img.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->docs.image.doc, doc.data(), doc.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->docs.image.off, seg_offsets, ((size_t)c->docs.n_docs + 1) * 8, hipMemcpyHostToDevice));
+  c->docs.image.n = n_segs;
   int rc = launch_reset(c);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1585,7 +1558,7 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
 }
 
 int mte_submit(mte_ctx* c, const mte_batch* b) {
-  if (!c || !b || b->n_docs != c->n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
+  if (!c || !b || b->n_docs != c->docs.n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
   if (b->op_offsets[0] != 0 || b->op_offsets[b->n_docs] != b->n_ops) return set_err(c, MTE_E_INVALID_ARG, "op_offsets");
   for (uint32_t d = 0; d < b->n_docs; d++)
     if (b->op_offsets[d + 1] < b->op_offsets[d]) return set_err(c, MTE_E_INVALID_ARG, "op_offsets not sorted");
@@ -1593,27 +1566,28 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
     if ((uint64_t)b->propsets[i].first + b->propsets[i].count > b->n_props)
       return set_err(c, MTE_E_INVALID_ARG, "propset %u out of range", i);
   if (c->arena_n + b->text_units >= (1ull << 32)) return set_err(c, MTE_E_OOM, "text arena exceeds 2^32 units");
-  if (c->d_refs && c->arena_n + b->text_units >= (1ull << 31))  // loaded markers are named above 2^31
+  if (c->docs.d_refs && c->arena_n + b->text_units >= (1ull << 31))  // loaded markers are named above 2^31
     return set_err(c, MTE_E_OOM, "text arena of a context with local references exceeds 2^31 units");
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   if (!c->up_stream) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->slot_ev[i], hipEventDisableTiming));
+    for (BatchSlot& s : c->slot) HIPCHK(c, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
   }
   // the other slot than the one mte_run replays now; its buffers are written
   // once the last run that read them is done
   const int w = c->submitted ? c->rslot ^ 1 : c->rslot;
   if (c->tail.joinable() && w == c->tail_slot) JOIN_TAIL(c);  // a second submit without mte_run
-  HIPCHK(c, hipStreamWaitEvent(c->up_stream, c->slot_ev[w], 0));
+  BatchSlot& s = c->slot[w];
+  HIPCHK(c, hipStreamWaitEvent(c->up_stream, s.ev, 0));
   // the replay kernels read the records in place; kRecPad zeroed records
   // follow the last one for the L2 prefetch that runs ahead
-  if ((rc = grow(c, &c->d_ops_s[w], &c->ops_cap_s[w], b->n_ops + kRecPad))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_ops_s[w] + b->n_ops, 0, kRecPad * sizeof(mte_op), c->up_stream));
-  if ((rc = grow(c, &c->d_off_s[w], &c->off_cap_s[w], (uint64_t)b->n_docs + 1))) return rc;
-  if ((rc = grow(c, &c->d_ps_s[w], &c->ps_cap_s[w], (uint64_t)b->n_propsets + 1))) return rc;
-  if ((rc = grow(c, &c->d_pe_s[w], &c->pe_cap_s[w], (uint64_t)b->n_props + 1))) return rc;
-  if ((rc = grow(c, &c->d_cps_s[w], &c->cps_cap_s[w], 2 * ((uint64_t)b->n_propsets + 1)))) return rc;
+  if ((rc = grow(c, s.ops, b->n_ops + kRecPad))) return rc;
+  HIPCHK(c, hipMemsetAsync(s.ops.p + b->n_ops, 0, kRecPad * sizeof(mte_op), c->up_stream));
+  if ((rc = grow(c, s.off, (uint64_t)b->n_docs + 1))) return rc;
+  if ((rc = grow(c, s.ps, (uint64_t)b->n_propsets + 1))) return rc;
+  if ((rc = grow(c, s.pe, (uint64_t)b->n_props + 1))) return rc;
+  if ((rc = grow(c, s.cps, 2 * ((uint64_t)b->n_propsets + 1)))) return rc;
   if (b->n_ops) {
     // every record is validated on the way (no kernel may index out of bounds);
     // the host validates and stages while the previous batch may replay
@@ -1623,26 +1597,26 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
       return rc == MTE_E_INVALID_ARG ? set_err(c, rc, "op %llu: %s", (unsigned long long)bad, why) : rc;
   } else {
     c->h_text_ps.clear();
-    c->h_rel_s[w].clear();
+    s.h_rel.clear();
   }
   // append batch text to the arena (a running replay reads only below arena_n;
   // growing it waits for the replay)
-  if ((rc = grow(c, &c->arena, &c->arena_cap, c->arena_n + b->text_units + 1, true, c->arena_n))) return rc;
+  if ((rc = grow(c, c->arena, c->arena_n + b->text_units + 1, true, c->arena_n))) return rc;
   if (b->text_units)
-    HIPCHK(c, hipMemcpyAsync(c->arena + c->arena_n, b->text, b->text_units * 2, hipMemcpyHostToDevice, c->up_stream));
+    HIPCHK(c, hipMemcpyAsync(c->arena.p + c->arena_n, b->text, b->text_units * 2, hipMemcpyHostToDevice, c->up_stream));
   c->h_arena.insert(c->h_arena.end(), b->text, b->text + b->text_units);
-  c->text_base_s[w] = (uint32_t)c->arena_n;
+  s.text_base = (uint32_t)c->arena_n;
   c->arena_n += b->text_units;
-  HIPCHK(c, hipMemcpyAsync(c->d_off_s[w], b->op_offsets, ((uint64_t)b->n_docs + 1) * 8, hipMemcpyHostToDevice,
+  HIPCHK(c, hipMemcpyAsync(s.off.p, b->op_offsets, ((uint64_t)b->n_docs + 1) * 8, hipMemcpyHostToDevice,
                            c->up_stream));
   if (b->n_propsets)
-    HIPCHK(c, hipMemcpyAsync(c->d_ps_s[w], b->propsets, b->n_propsets * sizeof(mte_propset), hipMemcpyHostToDevice,
+    HIPCHK(c, hipMemcpyAsync(s.ps.p, b->propsets, b->n_propsets * sizeof(mte_propset), hipMemcpyHostToDevice,
                              c->up_stream));
   if (b->n_props)
-    HIPCHK(c, hipMemcpyAsync(c->d_pe_s[w], b->props, b->n_props * sizeof(mte_prop), hipMemcpyHostToDevice,
+    HIPCHK(c, hipMemcpyAsync(s.pe.p, b->props, b->n_props * sizeof(mte_prop), hipMemcpyHostToDevice,
                              c->up_stream));
-  if (!c->h_sdocs.empty()) {
-    std::vector<uint32_t> order(c->h_sdocs);
+  if (!c->docs.h_sdocs.empty()) {
+    std::vector<uint32_t> order(c->docs.h_sdocs);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
       return b->op_offsets[x + 1] - b->op_offsets[x] > b->op_offsets[y + 1] - b->op_offsets[y];
     });
@@ -1650,26 +1624,25 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
     for (uint32_t d : order) in[d] = 1;
     for (uint32_t d = 0; d < b->n_docs; d++)
       if (!in[d]) order.push_back(d);
-    if ((rc = grow(c, &c->d_sorder_s[w], &c->sorder_cap_s[w], (uint64_t)b->n_docs))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_sorder_s[w], order.data(), (size_t)b->n_docs * 4, hipMemcpyHostToDevice,
+    if ((rc = grow(c, s.sorder, (uint64_t)b->n_docs))) return rc;
+    HIPCHK(c, hipMemcpyAsync(s.sorder.p, order.data(), (size_t)b->n_docs * 4, hipMemcpyHostToDevice,
                              c->up_stream));
     HIPCHK(c, hipStreamSynchronize(c->up_stream));  // `order` goes out of scope
   }
-  if (!c->h_htree_docs.empty()) {
+  if (!c->docs.h_htree_docs.empty()) {
     // the HBM tree pass's documents, most records first (the long chains start first)
     std::vector<uint32_t>& ho = c->h_hord;
-    ho = c->h_htree_docs;
+    ho = c->docs.h_htree_docs;
     std::stable_sort(ho.begin(), ho.end(), [&](uint32_t x, uint32_t y) {
       return b->op_offsets[x + 1] - b->op_offsets[x] > b->op_offsets[y + 1] - b->op_offsets[y];
     });
-    if ((rc = grow(c, &c->d_hord_s[w], &c->hord_cap_s[w], (uint64_t)ho.size()))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_hord_s[w], ho.data(), ho.size() * 4, hipMemcpyHostToDevice, c->up_stream));
+    if ((rc = grow(c, s.hord, (uint64_t)ho.size()))) return rc;
+    HIPCHK(c, hipMemcpyAsync(s.hord.p, ho.data(), ho.size() * 4, hipMemcpyHostToDevice, c->up_stream));
   }
-  c->hord_ok_s[w] = !c->h_htree_docs.empty();
-  if (!c->h_rel_s[w].empty()) {
-    if ((rc = grow(c, &c->d_rel_s[w], &c->rel_cap_s[w], (uint64_t)c->h_rel_s[w].size()))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_rel_s[w], c->h_rel_s[w].data(), c->h_rel_s[w].size() * 4, hipMemcpyHostToDevice,
-                             c->up_stream));
+  s.hord_ok = !c->docs.h_htree_docs.empty();
+  if (!s.h_rel.empty()) {
+    if ((rc = grow(c, s.rel, (uint64_t)s.h_rel.size()))) return rc;
+    HIPCHK(c, hipMemcpyAsync(s.rel.p, s.h_rel.data(), s.h_rel.size() * 4, hipMemcpyHostToDevice, c->up_stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->up_stream));  // host buffers may be freed after return
   // delta event regions of the MTE_DOC_EVENTS docs (per_op x records + 256
@@ -1677,42 +1650,40 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
   // use for each record that can slide references (a remote remove, an ack):
   // its slides and the MTE_DELTA_REFPOS snapshot after them
   {
-    std::vector<uint64_t>& off = c->h_dl_off_s[w];
+    std::vector<uint64_t>& off = s.h_dl_off;
     off.assign((size_t)b->n_docs + 1, 0);
     bool any = false;
     for (uint32_t d = 0; d < b->n_docs; d++) {
-      const bool e = d < c->h_events.size() && c->h_events[d];
+      const bool e = d < c->docs.h_events.size() && c->docs.h_events[d];
       any = any || e;
       uint64_t extra = 0;
-      if (e && d < c->h_slides.size() && c->h_slides[d]) {
-        uint32_t hi = c->h_ref_hi[d];
+      if (e && d < c->docs.h_slides.size() && c->docs.h_slides[d]) {
+        uint32_t hi = c->docs.h_ref_hi[d];
         uint64_t sliding = 0;
         for (uint64_t i = b->op_offsets[d]; i < b->op_offsets[d + 1]; i++) {
           const mte_op& o = b->ops[i];
           if (o.type == MTE_OP_REF && (uint32_t)o.pos2 + 1 > hi) hi = (uint32_t)o.pos2 + 1;
           if ((o.type == MTE_OP_REMOVE && !(o.flags & MTE_F_LOCAL)) || o.type == MTE_OP_ACK) sliding++;
         }
-        c->h_ref_hi[d] = hi;
+        c->docs.h_ref_hi[d] = hi;
         extra = sliding * 2 * (uint64_t)hi;
       }
       off[d + 1] = off[d] + (e ? (uint64_t)c->ev_per_op * (b->op_offsets[d + 1] - b->op_offsets[d]) + 256 + extra : 0);
     }
     if (any) {
-      if ((rc = grow(c, &c->d_dl_off_s[w], &c->dl_off_cap_s[w], (uint64_t)b->n_docs + 1))) return rc;
-      if ((rc = grow(c, &c->d_dl_s[w], &c->dl_cap_s[w], off[b->n_docs] + 1))) return rc;
-      if ((rc = grow(c, &c->d_dl_n_s[w], &c->dl_n_cap_s[w], (uint64_t)b->n_docs + 1))) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->d_dl_off_s[w], off.data(), off.size() * 8, hipMemcpyHostToDevice, c->up_stream));
-      HIPCHK(c, hipMemsetAsync(c->d_dl_n_s[w], 0, ((size_t)b->n_docs + 1) * 4, c->up_stream));
+      if ((rc = grow(c, s.dl_off, (uint64_t)b->n_docs + 1))) return rc;
+      if ((rc = grow(c, s.dl, off[b->n_docs] + 1))) return rc;
+      if ((rc = grow(c, s.dl_n, (uint64_t)b->n_docs + 1))) return rc;
+      HIPCHK(c, hipMemcpyAsync(s.dl_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->up_stream));
+      HIPCHK(c, hipMemsetAsync(s.dl_n.p, 0, ((size_t)b->n_docs + 1) * 4, c->up_stream));
       HIPCHK(c, hipStreamSynchronize(c->up_stream));
     } else {
       off.clear();
     }
   }
-  for (uint32_t i = 0; b->props && i < b->n_props; i++) {
-    c->max_vid = std::max(c->max_vid, b->props[i].value);
+  for (uint32_t i = 0; b->props && i < b->n_props; i++)
     if (b->props[i].key < MTE_MAX_KEYS)
       c->max_vid_k[b->props[i].key] = std::max(c->max_vid_k[b->props[i].key], b->props[i].value);
-  }
   // the keys of every propset a text insert or an annotate used (upload_ops)
   for (uint32_t i = 0; i < b->n_propsets && i < c->h_text_ps.size(); i++)
     if (c->h_text_ps[i]) {
@@ -1720,20 +1691,12 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
       for (uint32_t t = 0; t < ps.count; t++)
         if (b->props[ps.first + t].key < MTE_MAX_KEYS) c->key_text[b->props[ps.first + t].key] = 1;
     }
-  c->n_ops_s[w] = b->n_ops;
-  c->n_propsets_s[w] = b->n_propsets;
+  s.n_ops = b->n_ops;
+  s.n_propsets = b->n_propsets;
   uint64_t mx = 0;
   for (uint32_t d = 0; d < b->n_docs; d++) mx = std::max<uint64_t>(mx, b->op_offsets[d + 1] - b->op_offsets[d]);
-  c->max_doc_ops_s[w] = mx;
+  s.max_doc_ops = mx;
   c->rslot = w;
-  c->d_ops = c->d_ops_s[w];
-  c->d_cps = c->d_cps_s[w];
-  c->d_off = c->d_off_s[w];
-  c->d_ps = c->d_ps_s[w];
-  c->d_pe = c->d_pe_s[w];
-  c->n_ops = b->n_ops;
-  c->n_propsets = b->n_propsets;
-  c->batch_text_base = c->text_base_s[w];
   c->submitted = true;
   return MTE_OK;
 }
@@ -1742,38 +1705,39 @@ int mte_run(mte_ctx* c) {
   if (!c) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   if (!c->submitted) return set_err(c, MTE_E_STATE, "mte_run before mte_submit");
-  if (!c->n_docs) return MTE_OK;
+  if (!c->docs.n_docs) return MTE_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));  // kernel_ms covers every kernel of the run
-  hipLaunchKernelGGL(begin_batch_kernel, dim3((c->n_docs + 255) / 256), dim3(256), 0, c->stream, c->hdr, c->stats,
-                     c->n_docs);
+  hipLaunchKernelGGL(begin_batch_kernel, dim3((c->docs.n_docs + 255) / 256), dim3(256), 0, c->stream, c->docs.hdr,
+                     c->docs.stats, c->docs.n_docs);
   HIPCHK(c, hipGetLastError());
+  const BatchSlot& s = c->slot[c->rslot];
   ReplayArgs a;
-  a.hdr = c->hdr;
-  a.planes = (uint32_t*)c->soa.len;
-  a.stride = c->soa.plane_stride;
+  a.hdr = c->docs.hdr;
+  a.planes = (uint32_t*)c->docs.soa.len;
+  a.stride = c->docs.soa.plane_stride;
   a.cap = c->cap;
-  a.n_docs = c->n_docs;
-  a.recs = reinterpret_cast<const uint4*>(c->d_ops);
-  a.cps = c->d_cps;
-  a.op_off = c->d_off;
-  a.ps = c->d_ps;
-  a.pe = c->d_pe;
+  a.n_docs = c->docs.n_docs;
+  a.recs = reinterpret_cast<const uint4*>(s.ops.p);
+  a.cps = s.cps.p;
+  a.op_off = s.off.p;
+  a.ps = s.ps.p;
+  a.pe = s.pe.p;
   a.n_keys = c->n_keys;
-  a.text_base = c->batch_text_base;
-  a.stats = c->stats;
-  a.pair_docs = c->d_pairs;
-  a.n_pairs = c->n_pairs;
-  a.group = c->pass1_group;
+  a.text_base = s.text_base;
+  a.stats = c->docs.stats;
+  a.pair_docs = c->docs.d_pairs;
+  a.n_pairs = c->docs.n_pairs;
+  a.group = c->docs.pass1_group;
   a.wclock = nullptr;
-  const bool evs = !c->h_dl_off_s[c->rslot].empty();
-  a.dl = evs ? c->d_dl_s[c->rslot] : nullptr;
-  a.dl_off = evs ? c->d_dl_off_s[c->rslot] : nullptr;
-  a.dl_n = evs ? c->d_dl_n_s[c->rslot] : nullptr;
+  const bool evs = !s.h_dl_off.empty();  // some document of the batch records events
+  a.dl = evs ? s.dl.p : nullptr;
+  a.dl_off = evs ? s.dl_off.p : nullptr;
+  a.dl_n = evs ? s.dl_n.p : nullptr;
   c->ev_slot = evs ? c->rslot : -1;
-  a.refs = c->d_refs;
+  a.refs = c->docs.d_refs;
   a.ref_cap = c->ref_cap;
-  a.sorder = c->h_sdocs.empty() ? nullptr : c->d_sorder_s[c->rslot];
+  a.sorder = c->docs.h_sdocs.empty() ? nullptr : s.sorder.p;
   // s_memrealtime runs at 100 MHz: ticks = ms x 1e5, scaled to this batch's
   // ops.  A context's first run has no previous duration: it is estimated from
   // the batch, the larger of a saturated chip's throughput (0.215 ns per op,
@@ -1783,30 +1747,30 @@ int mte_run(mte_ctx* c) {
   // (DESIGN.md §6), which is what the schedule's bands need
   double eta_ms = 0.0;
   if (c->last_ms > 0 && c->last_ops > 0) {
-    eta_ms = c->last_ms * (double)c->n_ops / c->last_ops;
-  } else if (c->n_ops) {
-    const double thr = 2.15e-7 * (double)c->n_ops;
-    const double chain = 8.5e-4 * (double)c->max_doc_ops_s[c->rslot] * (double)c->pass1_group;
+    eta_ms = c->last_ms * (double)s.n_ops / c->last_ops;
+  } else if (s.n_ops) {
+    const double thr = 2.15e-7 * (double)s.n_ops;
+    const double chain = 8.5e-4 * (double)s.max_doc_ops * (double)c->docs.pass1_group;
     eta_ms = std::max(thr, chain);
   }
   a.eta = (unsigned long long)(eta_ms * 1e5);
   if (c->wclock_path) {
-    if (!c->d_wclock) HIPCHK(c, hipMalloc((void**)&c->d_wclock, 16ull * (c->n_pairs + 1)));
-    a.wclock = c->d_wclock;
+    if (!c->docs.d_wclock) HIPCHK(c, hipMalloc((void**)&c->docs.d_wclock, 16ull * (c->docs.n_pairs + 1)));
+    a.wclock = c->docs.d_wclock;
   }
-  if (c->n_rs) {
-    hipLaunchKernelGGL(round_sync_kernel, dim3((c->n_rs + 3) / 4), dim3(256), 0, c->stream, c->hdr, a.recs, c->d_off,
-                       c->d_rs_docs, c->n_rs);
+  if (c->docs.n_rs) {
+    hipLaunchKernelGGL(round_sync_kernel, dim3((c->docs.n_rs + 3) / 4), dim3(256), 0, c->stream, c->docs.hdr, a.recs,
+                       s.off.p, c->docs.d_rs_docs, c->docs.n_rs);
     HIPCHK(c, hipGetLastError());
   }
-  if (const uint32_t nr = (uint32_t)c->h_rel_s[c->rslot].size()) {
-    hipLaunchKernelGGL(rel_route_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, c->hdr,
-                       c->d_rel_s[c->rslot], nr, c->chunked ? 1 : 0);
+  if (const uint32_t nr = (uint32_t)s.h_rel.size()) {
+    hipLaunchKernelGGL(rel_route_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, c->docs.hdr,
+                       s.rel.p, nr, c->docs.chunked ? 1 : 0);
     HIPCHK(c, hipGetLastError());
   }
-  if (c->n_propsets) {
-    hipLaunchKernelGGL(props_kernel, dim3((uint32_t)((c->n_propsets + 255) / 256)), dim3(256), 0, c->stream, c->d_ps,
-                       (uint32_t)c->n_propsets, c->d_pe, c->n_keys, c->d_cps);
+  if (s.n_propsets) {
+    hipLaunchKernelGGL(props_kernel, dim3((uint32_t)((s.n_propsets + 255) / 256)), dim3(256), 0, c->stream, s.ps.p,
+                       (uint32_t)s.n_propsets, s.pe.p, c->n_keys, s.cps.p);
     HIPCHK(c, hipGetLastError());
   }
   int rc;
@@ -1819,9 +1783,9 @@ int mte_run(mte_ctx* c) {
   c->ran = true;
   const int slot = c->rslot;
   auto finish = [c, slot]() -> int {
-    if (c->n_tree || c->n_htree) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    if (c->docs.n_tree || c->docs.n_htree) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventRecord(c->slot_ev[slot], c->stream));  // the slot may be rewritten after this
+    HIPCHK(c, hipEventRecord(c->slot[slot].ev, c->stream));  // the slot may be rewritten after this
     return MTE_OK;
   };
   if (!c->tail_fn) return finish();
@@ -1846,12 +1810,12 @@ int mte_sync(mte_ctx* c) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess && ms > 0.f) {
       c->last_ms = ms;
-      c->last_ops = (double)c->n_ops;
+      c->last_ops = (double)c->slot[c->rslot].n_ops;  // the batch last submitted
     }
   }
-  if (c->wclock_path && c->d_wclock) {
-    std::vector<unsigned long long> w(2ull * c->n_pairs);
-    HIPCHK(c, hipMemcpy(w.data(), c->d_wclock, w.size() * 8, hipMemcpyDeviceToHost));
+  if (c->wclock_path && c->docs.d_wclock) {
+    std::vector<unsigned long long> w(2ull * c->docs.n_pairs);
+    HIPCHK(c, hipMemcpy(w.data(), c->docs.d_wclock, w.size() * 8, hipMemcpyDeviceToHost));
     if (FILE* f = std::fopen(c->wclock_path, "wb")) {
       std::fwrite(w.data(), 8, w.size(), f);
       std::fclose(f);
@@ -1868,37 +1832,37 @@ int mte_reset(mte_ctx* c) {
 }
 
 int mte_digest_device(mte_ctx* c, void* out, uint32_t n_docs) {
-  if (!c || !out || n_docs != c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !out || n_docs != c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   if (!n_docs) return MTE_OK;
   HIPCHK(c, hipSetDevice(c->device));
   DigestArgs a;
-  a.hdr = c->hdr;
-  a.soa = c->soa;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
   a.cap = c->cap;
   a.n_keys = c->n_keys;
-  a.n_docs = c->n_docs;
-  a.arena = c->arena;
+  a.n_docs = c->docs.n_docs;
+  a.arena = c->arena.p;
   a.pow1 = c->d_pow;
   a.pow2 = c->d_pow + 32;
   a.out = (uint64_t*)out;
   if (c->cap > kDgWaveMaxCap) {
     // documents of up to `cap` segments: tile-parallel (dg_*_kernel)
-    if (!c->d_dgt) {
-      DigestTiles& t = c->dgt;
+    if (!c->docs.d_dgt) {
+      DigestTiles& t = c->docs.dgt;
       t.tpd = (c->cap + kDgTile - 1) / kDgTile;
-      const uint64_t nt = (uint64_t)c->n_docs * t.tpd;
-      HIPCHK(c, hipMalloc(&c->d_dgt, nt * (4 + 24) + 4ull * c->n_docs + 64));
-      t.part = (uint64_t*)c->d_dgt;
+      const uint64_t nt = (uint64_t)c->docs.n_docs * t.tpd;
+      HIPCHK(c, hipMalloc(&c->docs.d_dgt, nt * (4 + 24) + 4ull * c->docs.n_docs + 64));
+      t.part = (uint64_t*)c->docs.d_dgt;
       t.tsum = (int32_t*)(t.part + 3 * nt);
       t.tot = t.tsum + nt;
     }
-    const uint64_t nt = (uint64_t)n_docs * c->dgt.tpd;
+    const uint64_t nt = (uint64_t)n_docs * c->docs.dgt.tpd;
     const uint32_t tb = (uint32_t)((nt + 3) / 4);
-    hipLaunchKernelGGL(dg_len_kernel, dim3(tb), dim3(256), 0, c->stream, a, c->dgt);
-    hipLaunchKernelGGL(dg_scan_kernel, dim3(n_docs), dim3(256), 0, c->stream, a, c->dgt);
-    hipLaunchKernelGGL(dg_tile_kernel, dim3(tb), dim3(256), 0, c->stream, a, c->dgt);
-    hipLaunchKernelGGL(dg_final_kernel, dim3((n_docs + 3) / 4), dim3(256), 0, c->stream, a, c->dgt);
+    hipLaunchKernelGGL(dg_len_kernel, dim3(tb), dim3(256), 0, c->stream, a, c->docs.dgt);
+    hipLaunchKernelGGL(dg_scan_kernel, dim3(n_docs), dim3(256), 0, c->stream, a, c->docs.dgt);
+    hipLaunchKernelGGL(dg_tile_kernel, dim3(tb), dim3(256), 0, c->stream, a, c->docs.dgt);
+    hipLaunchKernelGGL(dg_final_kernel, dim3((n_docs + 3) / 4), dim3(256), 0, c->stream, a, c->docs.dgt);
   } else {
     hipLaunchKernelGGL(digest_kernel, dim3((n_docs + kDocsPerBlock - 1) / kDocsPerBlock), dim3(256), 0, c->stream, a);
   }
@@ -1907,49 +1871,49 @@ int mte_digest_device(mte_ctx* c, void* out, uint32_t n_docs) {
 }
 
 int mte_digest(mte_ctx* c, uint64_t* out, uint32_t n_docs) {
-  if (!c || !out || n_docs != c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !out || n_docs != c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   if (!n_docs) return MTE_OK;
-  int rc = mte_digest_device(c, c->d_digest, n_docs);
+  int rc = mte_digest_device(c, c->docs.d_digest, n_docs);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, c->d_digest, sizeof(uint64_t) * 4 * n_docs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->docs.d_digest, sizeof(uint64_t) * 4 * n_docs, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MTE_OK;
 }
 
 int mte_doc_status(mte_ctx* c, int32_t* out, uint32_t n_docs) {
-  if (!c || !out || n_docs != c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !out || n_docs != c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   if (!n_docs) return MTE_OK;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<DocHdr> h(n_docs);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->hdr, sizeof(DocHdr) * n_docs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.data(), c->docs.hdr, sizeof(DocHdr) * n_docs, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (uint32_t i = 0; i < n_docs; i++) out[i] = h[i].status;
   return MTE_OK;
 }
 
 int mte_read_doc(mte_ctx* c, uint32_t doc, mte_doc_view* v) {
-  if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !v || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   HIPCHK(c, hipSetDevice(c->device));
   DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t n = (uint32_t)std::max(h.nseg, 0);
   const uint64_t db = (uint64_t)doc * c->cap;
   std::vector<int32_t> len(n + 1), rseq(n + 1);
   std::vector<uint32_t> meta(n + 1), toff(n + 1), props((size_t)(n + 1) * (c->n_keys ? c->n_keys : 1));
   std::vector<uint32_t> tw(n + 1, 0u);  // tree words (legacy documents)
-  if (n && c->d_tree && c->h_legacy[doc])
-    HIPCHK(c, hipMemcpyAsync(tw.data(), c->d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (n && c->docs.d_tree && c->docs.h_legacy[doc])
+    HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (n) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->soa.len + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->soa.rseq + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(meta.data(), c->soa.meta + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->soa.toff + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->docs.soa.rseq + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(meta.data(), c->docs.soa.meta + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, n * 4, hipMemcpyDeviceToHost, c->stream));
     for (uint32_t k = 0; k < c->n_keys; k++)
-      HIPCHK(c, hipMemcpyAsync(props.data() + (size_t)k * n, c->soa.props + k * c->soa.plane_stride + db, n * 4,
+      HIPCHK(c, hipMemcpyAsync(props.data() + (size_t)k * n, c->docs.soa.props + k * c->docs.soa.plane_stride + db, n * 4,
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -1995,7 +1959,7 @@ int mte_set_event_capacity(mte_ctx* c, uint32_t per_op) {
 int mte_set_ref_capacity(mte_ctx* c, uint32_t per_doc) {
   if (!c || per_doc == 0 || per_doc > (1u << 20)) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (c->d_refs) return set_err(c, MTE_E_STATE, "mte_set_ref_capacity after mte_load_docs of MTE_DOC_REFS documents");
+  if (c->docs.d_refs) return set_err(c, MTE_E_STATE, "mte_set_ref_capacity after mte_load_docs of MTE_DOC_REFS documents");
   c->ref_cap = per_doc;
   return MTE_OK;
 }
@@ -2005,13 +1969,13 @@ int mte_set_ref_capacity(mte_ctx* c, uint32_t per_doc) {
 // offset there (0 on a removed segment); -1 for a detached or unused slot or a
 // unit no segment holds any more (a tombstone compacted at minSeq)
 static int read_refs_view(mte_ctx* c, uint32_t doc, int32_t* pos, uint32_t n, bool transient) {
-  if (!c || (n && !pos) || doc >= c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || (n && !pos) || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (c->h_refs.empty() || !c->h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
+  if (c->docs.h_refs.empty() || !c->docs.h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
   if (n > c->ref_cap) return set_err(c, MTE_E_INVALID_ARG, "%u reference slots > capacity %u", n, c->ref_cap);
   HIPCHK(c, hipSetDevice(c->device));
   DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t ns = (uint32_t)std::max(h.nseg, 0);
   const uint64_t db = (uint64_t)doc * c->cap;
@@ -2020,16 +1984,16 @@ static int read_refs_view(mte_ctx* c, uint32_t doc, int32_t* pos, uint32_t n, bo
   std::vector<uint2> rt(n + 1);
   std::vector<uint32_t> tw;  // tree words, for Transient references (their leaf ids)
   if (ns) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->soa.rseq + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->d_tree) {
+    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->docs.soa.rseq + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    if (c->docs.d_tree) {
       tw.resize(ns);
-      HIPCHK(c, hipMemcpyAsync(tw.data(), c->d_tree + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
     }
   }
   if (n)
-    HIPCHK(c, hipMemcpyAsync(rt.data(), c->d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
+    HIPCHK(c, hipMemcpyAsync(rt.data(), c->docs.d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (uint32_t r = 0; r < n; r++) {
@@ -2068,13 +2032,13 @@ int mte_read_refs_transient(mte_ctx* c, uint32_t doc, int32_t* pos, uint32_t n) 
 }
 
 int mte_read_ref_order(mte_ctx* c, uint32_t doc, int64_t* key, uint32_t n) {
-  if (!c || (n && !key) || doc >= c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || (n && !key) || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (c->h_refs.empty() || !c->h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
+  if (c->docs.h_refs.empty() || !c->docs.h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
   if (n > c->ref_cap) return set_err(c, MTE_E_INVALID_ARG, "%u reference slots > capacity %u", n, c->ref_cap);
   HIPCHK(c, hipSetDevice(c->device));
   DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t ns = (uint32_t)std::max(h.nseg, 0);
   const uint64_t db = (uint64_t)doc * c->cap;
@@ -2082,11 +2046,11 @@ int mte_read_ref_order(mte_ctx* c, uint32_t doc, int64_t* key, uint32_t n) {
   std::vector<uint32_t> toff(ns + 1);
   std::vector<uint2> rt(n + 1);
   if (ns) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (n)
-    HIPCHK(c, hipMemcpyAsync(rt.data(), c->d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
+    HIPCHK(c, hipMemcpyAsync(rt.data(), c->docs.d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (uint32_t r = 0; r < n; r++) {
@@ -2107,49 +2071,50 @@ int mte_read_ref_order(mte_ctx* c, uint32_t doc, int64_t* key, uint32_t n) {
 }
 
 int mte_read_deltas(mte_ctx* c, uint32_t doc, mte_delta* out, uint64_t cap, uint64_t* n) {
-  if (!c || !n || doc >= c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !n || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   *n = 0;
-  if (c->h_events.empty() || !c->h_events[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_EVENTS", doc);
+  if (c->docs.h_events.empty() || !c->docs.h_events[doc])
+    return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_EVENTS", doc);
   if (c->ev_slot < 0) return MTE_OK;  // no batch with events ran yet
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int sl = c->ev_slot;
+  const BatchSlot& sl = c->slot[c->ev_slot];
   uint32_t cnt = 0;
-  HIPCHK(c, hipMemcpy(&cnt, c->d_dl_n_s[sl] + doc, 4, hipMemcpyDeviceToHost));
-  const uint64_t b0 = c->h_dl_off_s[sl][doc], room = c->h_dl_off_s[sl][doc + 1] - b0;
+  HIPCHK(c, hipMemcpy(&cnt, sl.dl_n.p + doc, 4, hipMemcpyDeviceToHost));
+  const uint64_t b0 = sl.h_dl_off[doc], room = sl.h_dl_off[doc + 1] - b0;
   *n = cnt;
   if (cnt > room) return set_err(c, MTE_E_CAPACITY, "doc %u: %u delta events, room for %llu (mte_set_event_capacity)",
                                  doc, cnt, (unsigned long long)room);
   const uint64_t k = std::min<uint64_t>(cap, cnt);
-  if (out && k) HIPCHK(c, hipMemcpy(out, c->d_dl_s[sl] + b0, k * sizeof(mte_delta), hipMemcpyDeviceToHost));
+  if (out && k) HIPCHK(c, hipMemcpy(out, sl.dl.p + b0, k * sizeof(mte_delta), hipMemcpyDeviceToHost));
   return MTE_OK;
 }
 
 int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
-  if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !v || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   HIPCHK(c, hipSetDevice(c->device));
   DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t n = (uint32_t)std::max(h.nseg, 0);
   const uint64_t db = (uint64_t)doc * c->cap;
   const uint32_t np = kFieldPlanes + c->n_keys;
   std::vector<uint32_t> pl((size_t)np * (n + 1));
   std::vector<uint32_t> tw(n + 1, 0u);
-  if (n && c->d_tree && c->h_legacy[doc])
-    HIPCHK(c, hipMemcpyAsync(tw.data(), c->d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (n && c->docs.d_tree && c->docs.h_legacy[doc])
+    HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
   for (uint32_t p = 0; p < np && n; p++)
-    HIPCHK(c, hipMemcpyAsync(pl.data() + (size_t)p * n, reinterpret_cast<const uint32_t*>(c->soa.len) +
-                                                             p * c->soa.plane_stride + db,
+    HIPCHK(c, hipMemcpyAsync(pl.data() + (size_t)p * n, reinterpret_cast<const uint32_t*>(c->docs.soa.len) +
+                                                             p * c->docs.soa.plane_stride + db,
                              n * 4, hipMemcpyDeviceToHost, c->stream));
   // the removers of short ids >= 32 (mte_htree.h kRmHiPlane): mte_seg.removers has 32 bits
   std::vector<uint32_t> rmh;
-  if (n && !c->h_local.empty() && c->h_local[doc]) {
+  if (n && !c->docs.h_local.empty() && c->docs.h_local[doc]) {
     rmh.resize(n);
-    HIPCHK(c, hipMemcpyAsync(rmh.data(), reinterpret_cast<const uint32_t*>(c->soa.len) +
-                                             (uint64_t)(kFieldPlanes + 3 * c->kt + 5) * c->soa.plane_stride + db,
+    HIPCHK(c, hipMemcpyAsync(rmh.data(), reinterpret_cast<const uint32_t*>(c->docs.soa.len) +
+                                             (uint64_t)(kFieldPlanes + 3 * c->kt + 5) * c->docs.soa.plane_stride + db,
                              n * 4, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2165,7 +2130,7 @@ int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
   // reference's scour does in its own time, mergeTree.ts:681-747).  No later
   // op sees them and a summary leaves them out (snapshotV1.ts:195-199): the
   // list is the canonical one, without them.
-  const bool lazy_zamboni = c->rounds_carried && !c->h_legacy[doc];
+  const bool lazy_zamboni = c->docs.rounds_carried && !c->docs.h_legacy[doc];
   for (uint32_t i = 0; i < n; i++) {
     const int32_t len = (int32_t)pl[i], rseq = (int32_t)pl[2 * (size_t)n + i];
     const uint32_t meta = pl[4 * (size_t)n + i], kind = meta >> 8;
@@ -2259,11 +2224,11 @@ int mte_comm_share(mte_ctx* c, const mte_ctx* src) {
 
 namespace {
 int comm_staging(mte_ctx* c, uint64_t n) {
-  if (n <= c->comm_cap) return MTE_OK;
-  if (c->d_comm) HIPCHK(c, hipFree(c->d_comm));
-  c->d_comm = nullptr;
-  HIPCHK(c, hipMalloc((void**)&c->d_comm, n * sizeof(uint64_t)));
-  c->comm_cap = n;
+  if (n <= c->d_comm.cap) return MTE_OK;
+  if (c->d_comm.p) HIPCHK(c, hipFree(c->d_comm.p));
+  c->d_comm = DevBuf<uint64_t>{};
+  HIPCHK(c, hipMalloc((void**)&c->d_comm.p, n * sizeof(uint64_t)));
+  c->d_comm.cap = n;
   return MTE_OK;
 }
 }  // namespace
@@ -2275,7 +2240,7 @@ int mte_comm_allreduce_f64(mte_ctx* c, double* v, int op) {
   HIPCHK(c, hipSetDevice(c->device));
   int rc = comm_staging(c, 1);
   if (rc) return rc;
-  double* d = reinterpret_cast<double*>(c->d_comm);
+  double* d = reinterpret_cast<double*>(c->d_comm.p);
   HIPCHK(c, hipMemcpyAsync(d, v, sizeof(double), hipMemcpyHostToDevice, c->stream));
   NCCLCHK(c, ncclAllReduce(d, d, 1, ncclFloat64, op == MTE_COMM_SUM ? ncclSum : ncclMax, c->comm, c->stream));
   HIPCHK(c, hipMemcpyAsync(v, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2296,7 +2261,7 @@ int mte_comm_world(const mte_ctx* c, int32_t* world, int32_t* rank) {
 }
 
 int mte_comm_gather_digests(mte_ctx* c, uint64_t* out, uint64_t out_cap, uint32_t docs_per_rank) {
-  if (!c || !out || docs_per_rank < c->n_docs) return MTE_E_INVALID_ARG;
+  if (!c || !out || docs_per_rank < c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   if (!c->comm) return set_err(c, MTE_E_STATE, "mte_comm_init first");
   if (out_cap < 4ull * docs_per_rank * (uint64_t)c->world)
@@ -2306,11 +2271,11 @@ int mte_comm_gather_digests(mte_ctx* c, uint64_t* out, uint64_t out_cap, uint32_
   const uint64_t per = 4ull * docs_per_rank;
   int rc = comm_staging(c, per * (uint64_t)(c->world + 1));
   if (rc) return rc;
-  uint64_t* send = c->d_comm + per * (uint64_t)c->world;  // after the receive area
+  uint64_t* send = c->d_comm.p + per * (uint64_t)c->world;  // after the receive area
   HIPCHK(c, hipMemsetAsync(send, 0, per * sizeof(uint64_t), c->stream));
-  if (c->n_docs && (rc = mte_digest_device(c, send, c->n_docs))) return rc;
-  NCCLCHK(c, ncclAllGather(send, c->d_comm, per, ncclUint64, c->comm, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->d_comm, per * (uint64_t)c->world * sizeof(uint64_t), hipMemcpyDeviceToHost,
+  if (c->docs.n_docs && (rc = mte_digest_device(c, send, c->docs.n_docs))) return rc;
+  NCCLCHK(c, ncclAllGather(send, c->d_comm.p, per, ncclUint64, c->comm, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_comm.p, per * (uint64_t)c->world * sizeof(uint64_t), hipMemcpyDeviceToHost,
                            c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MTE_OK;
@@ -2331,13 +2296,13 @@ int mte_stats_get(mte_ctx* c, mte_stats* o) {
   if (!c || !o) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   std::memset(o, 0, sizeof(*o));
-  if (!c->n_docs) return MTE_OK;
+  if (!c->docs.n_docs) return MTE_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<unsigned long long> s((size_t)c->n_docs * kNumStats);
+  std::vector<unsigned long long> s((size_t)c->docs.n_docs * kNumStats);
   unsigned long long chunk_canon = 0;
-  HIPCHK(c, hipMemcpyAsync(s.data(), c->stats, s.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s.data(), c->docs.stats, s.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (uint32_t d = 0; d < c->n_docs; d++) {
+  for (uint32_t d = 0; d < c->docs.n_docs; d++) {
     const unsigned long long* x = &s[(size_t)d * kNumStats];
     o->ops_applied += x[kStOps];
     o->segs_scanned += x[kStScanned];
@@ -2367,9 +2332,9 @@ int mte_stats_get(mte_ctx* c, mte_stats* o) {
   // entries they scanned instead of the document's S_live
   // the round phases' own bytes of the last run (RoundArgs::acct)
   o->round_bytes = 0.0;
-  if (c->chunked && c->rd.acct && c->n_docs) {
-    std::vector<unsigned long long> ac(c->n_docs);
-    HIPCHK(c, hipMemcpyAsync(ac.data(), c->rd.acct, sizeof(unsigned long long) * c->n_docs, hipMemcpyDeviceToHost,
+  if (c->docs.chunked && c->docs.rd.acct && c->docs.n_docs) {
+    std::vector<unsigned long long> ac(c->docs.n_docs);
+    HIPCHK(c, hipMemcpyAsync(ac.data(), c->docs.rd.acct, sizeof(unsigned long long) * c->docs.n_docs, hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (unsigned long long v : ac) o->round_bytes += (double)v;

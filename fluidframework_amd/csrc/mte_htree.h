@@ -29,6 +29,7 @@
 // that stores ends with vm_drain, as in mte_stream.h.
 #pragma once
 
+#include "mte_passes.h"
 #include "mte_stream.h"
 #include "mte_tree.h"
 
@@ -40,17 +41,11 @@ namespace mte {
 constexpr int kHE = MTE_HTREE_KHE;     // items per lane per tile
 constexpr int kHT = kWave * kHE;       // items per tile
 constexpr uint32_t kHdrTreeHbm = kHdrTreeHbmFlag;  // a legacy document continues on the HBM tree pass
-constexpr int kHtState = 8;            // state words per document
-
-// state words (HtreeArgs::st)
-enum HtSt { kHsDepth = 0, kHsNextId, kHsHeapN, kHsLseq, kHsRhi, kHsEntered, kHsWin };
-
 // MTE_HTREE_PROF (a profiling build only, `make prof`): per-phase clocks
 // (s_memrealtime ticks, 100 MHz) summed over every document into
 // HtreeArgs::prof: 0 insert, 1 remove / annotate, 2 ack, 3 zamboni (inside the
 // others too), 4 rollback / regen, 5 references / relative positions, 6 every
 // record, 7 records.
-constexpr int kHtProf = 8;
 #ifdef MTE_HTREE_PROF
 #define HPROF_BEGIN(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime();
 #define HPROF_END(h, i, v) (h).prof[i] += __builtin_amdgcn_s_memrealtime() - (v);
@@ -58,21 +53,6 @@ constexpr int kHtProf = 8;
 #define HPROF_BEGIN(v)
 #define HPROF_END(h, i, v)
 #endif
-
-struct HtreeArgs {
-  uint32_t* tree;        // tree words: tree[doc * cap + i]
-  const uint2* rheap;    // the register tiers' heaps (kTreeHeapCap + 1 per doc): an escalating doc's
-  uint2* heap;           // HBM tree heaps: heap[doc * (hcap + 1) + k], k = 1 .. hn
-  uint32_t hcap;
-  uint32_t lcap;         // items a document may hold in LDS (0: none; the launch's dynamic LDS)
-  uint32_t* st;          // kHtState words per document
-  int32_t* scr;          // L at scr[doc * 2 cap + i], P at scr[doc * 2 cap + cap + i]
-  const uint32_t* docs;  // the documents this pass may replay
-  uint32_t n_docs;
-  const uint16_t* arena;
-  unsigned long long* prof;  // kHtProf phase clocks (MTE_HTREE_PROF builds), or nullptr
-  uint32_t maint;        // some document records maintenance (the htree_kernel<K, S, true> build)
-};
 
 // plane indices of a local-client document (after the K property planes)
 template <int K> constexpr int kPkPlane = kFieldPlanes + K;
@@ -97,7 +77,6 @@ template <int K> constexpr int kRgPlane = kFieldPlanes + 3 * K + 4;
 // plane 3 holds 0 .. 31), zero while the item is not removed; the last plane
 // of every document with nP = kLocalPlanes (local-client and MTE_DOC_TREE ones)
 template <int K> constexpr int kRmHiPlane = kFieldPlanes + 3 * K + 5;
-template <int K> constexpr int kLocalPlanes = kFieldPlanes + 3 * K + 6;  // planes of a local-client / MTE_DOC_TREE document
 
 struct HT {
   uint32_t* pl;   // the document's plane base

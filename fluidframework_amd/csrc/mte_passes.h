@@ -1,7 +1,10 @@
-// mte_passes.h — host launchers of the replay passes.  Each pass lives in its
-// own translation unit (mte_pass_tree.hip, mte_pass_flat.hip,
+// mte_passes.h — the host-device contract of the replay passes: their host
+// launchers, the argument structs the launchers take and the layout constants
+// both sides use.  Each pass lives in its own translation unit
+// (mte_pass_tree.hip, mte_pass_htree.hip, mte_pass_flat.hip,
 // mte_pass_chunk.hip) so the passes compile in parallel and one can be rebuilt
-// alone; mte_engine.hip drives them (launch_replay).
+// alone; mte_engine.hip drives them (launch_replay) and includes no kernel
+// header.  The pass headers include this one for the declarations below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,10 +13,104 @@
 
 namespace mte {
 
-struct ReplayArgs;
-struct TreeArgs;
-struct HtreeArgs;
-struct ChunkArgs;
+// ---- the chunked pass (mte_chunk.h) -----------------------------------------
+constexpr uint32_t kChunkMinCap = 8192;  // ctxs with a smaller capacity use pass 3 = stream_kernel
+constexpr int kChE = 4;                  // slots per lane
+constexpr int kChSlots = kWave * kChE;   // 256 slots per chunk
+constexpr int kChFill = 128;             // segments per chunk after a re-layout
+constexpr int kChGroup = 64;             // chunks per summary group
+constexpr int kChWaves = 8;              // one document per 512-thread workgroup
+constexpr uint32_t kChMaxGroups = 500;   // G in LDS: 32 x 500 x 4 B
+
+struct ChunkArgs {
+  uint32_t* arena;   // plane p, doc d, chunk i, slot j: arena[p * astride + (d * nch_cap + i) * 256 + j]
+  uint64_t astride;
+  uint32_t nch_cap;  // chunks per doc
+  uint32_t ng_cap;   // groups per doc (<= kChMaxGroups)
+  uint32_t* cnt;     // [doc][nch_cap] segments per chunk
+  uint32_t* kc;      // [doc][nch_cap] re-layout scratch
+  int32_t* sum;      // [doc][MTE_MAX_CLIENTS][nch_cap]
+  // round phases (mte_round.h): with a plan, chunk_kernel replays only the
+  // documents the plan sends op after op, up to their run's end
+  const uint4* plan;      // [doc] x mode, y k0, z k1, w M (null: every escalated doc to its end)
+  const uint32_t* rflag;  // [doc] non-zero: the round phases left the run to this pass
+};
+
+// the workgroup's control block, after the G columns in the launch's dynamic LDS
+struct ChCtl {
+  int32_t req, arg_c, arg_r;
+  int32_t n;        // segments of the doc
+  int32_t nch;      // chunks in use
+  int32_t min_seq;  // for the re-layout's zamboni and the rebuilds
+  int32_t status;
+  int32_t part[kChWaves];
+  int32_t rr[MTE_MAX_CLIENTS];  // refSeq each summary column is valid for
+  int32_t pf_k;     // wave 0's current op (the prefetch wave runs ahead of it)
+  int32_t pf_stop;  // wave 0 left its op loop
+};
+
+// ---- the tree pass (mte_tree.h) ---------------------------------------------
+constexpr int kTreeHeapCap = 255;  // entries per document (+ the unused index 0)
+constexpr uint32_t kHdrTreeEsc = 0x40000000u;  // tree pass: the document is TIER 1's (E = 4)
+constexpr uint32_t kHdrTreeBig = 0x20000000u;  // tree pass: the document is TIER 2's (E = 8, 16)
+constexpr uint32_t kHdrTreeHbmFlag = 0x10000000u;  // past TIER 2: the HBM tree pass (mte_htree.h kHdrTreeHbm)
+// the tree word's bits (mte_tree.h describes the word)
+constexpr uint32_t kTH = 0x7u, kTCont = 0x8u, kTNsShift = 4, kTNs = 0x30u, kTPo = 0x40u, kTEmpty = 0x80u;
+constexpr uint32_t kTNl = 0x80000000u;
+constexpr uint16_t kRecNl = 0x8000u;  // op record flag (engine-internal): the insert's text holds a '\n'
+constexpr uint32_t kIdLimit = 1u << 23;
+
+struct TreeArgs {
+  uint32_t* tree;        // tree word of slot x of doc d: tree[d * cap + x]
+  uint2* heap;           // doc d: heap[d * (kTreeHeapCap + 1) + k], k = 1 .. size
+  const uint32_t* docs;  // the legacy documents
+  uint32_t n_docs;
+  const uint16_t* arena; // text (an append-merge looks at the last unit of a leaf)
+  uint32_t final_round;  // TIER 1: keep documents that shrink (no return to TIER 0)
+  uint32_t k_cap;        // this round's op cursor limit (TIER 0 / 1): documents advance together
+};
+
+// ---- the HBM tree pass (mte_htree.h) ----------------------------------------
+constexpr int kHtState = 8;            // state words per document
+
+// state words (HtreeArgs::st)
+enum HtSt { kHsDepth = 0, kHsNextId, kHsHeapN, kHsLseq, kHsRhi, kHsEntered, kHsWin };
+
+constexpr int kHtProf = 8;  // phase clocks of an MTE_HTREE_PROF build (mte_htree.h)
+
+struct HtreeArgs {
+  uint32_t* tree;        // tree words: tree[doc * cap + i]
+  const uint2* rheap;    // the register tiers' heaps (kTreeHeapCap + 1 per doc): an escalating doc's
+  uint2* heap;           // HBM tree heaps: heap[doc * (hcap + 1) + k], k = 1 .. hn
+  uint32_t hcap;
+  uint32_t lcap;         // items a document may hold in LDS (0: none; the launch's dynamic LDS)
+  uint32_t* st;          // kHtState words per document
+  int32_t* scr;          // L at scr[doc * 2 cap + i], P at scr[doc * 2 cap + cap + i]
+  const uint32_t* docs;  // the documents this pass may replay
+  uint32_t n_docs;
+  const uint16_t* arena;
+  unsigned long long* prof;  // kHtProf phase clocks (MTE_HTREE_PROF builds), or nullptr
+  uint32_t maint;        // some document records maintenance (the htree_kernel<K, S, true> build)
+};
+
+template <int K> constexpr int kLocalPlanes = kFieldPlanes + 3 * K + 6;  // planes of a local-client / MTE_DOC_TREE document
+
+// ---- local references (MTE_DOC_REFS, include/mte.h; mte_stream.h) -----------
+// A reference is kept as the text unit it sits on -- its arena offset (a
+// marker's is its reserved unit): splits never copy text, so the unit names the
+// same place in whatever segment holds it, which is what LocalReferenceCollection
+// keeps as (segment, offset) and moves on split (localReference.ts:391-416).
+// kRefOff (with kRefDetached): a reference slideAckedRemovedSegmentReferences
+// took off its segment's list for want of a segment to slide to
+// (mergeTree.ts:935-942, removeLocalRef keeps the segment): detached for
+// every read but mte_read_refs_transient, which still finds its segment.
+constexpr uint32_t kRefLive = 0x80000000u, kRefDetached = 0x40000000u, kRefOff = 0x20000000u;
+// a Transient reference (localReference.ts:263: never on its segment's list, so
+// nothing moves or slides it): kRefLive | kRefDetached | kRefTrans | its offset
+// in its segment, x = that segment's leaf id (mte_htree.h ht_ref_transient;
+// titems.c REF_TRANS): read as its segment's position + the offset, the offset
+// dropped once the segment is removed, -1 once the segment is gone
+constexpr uint32_t kRefTrans = 0x10000000u, kRefTransOff = 0x0fffffffu;
 
 // round phases of the chunked pass (mte_round.h)
 constexpr int kRB = 62;              // sub-ops per chunk and run: 128 + 2 x 62 slots <= 254

@@ -21,6 +21,7 @@
 // exists so that no document size is refused below the ctx capacity.
 #pragma once
 
+#include "mte_passes.h"
 #include "mte_replay.h"
 #include "mte_tree.h"
 
@@ -110,21 +111,7 @@ __device__ __forceinline__ int32_t own_prefix(const uint32_t* pl, uint64_t sd, i
 }
 
 // ---- local references (MTE_DOC_REFS, include/mte.h) -------------------------
-// A reference is kept as the text unit it sits on -- its arena offset (a
-// marker's is its reserved unit): splits never copy text, so the unit names the
-// same place in whatever segment holds it, which is what LocalReferenceCollection
-// keeps as (segment, offset) and moves on split (localReference.ts:391-416).
-// kRefOff (with kRefDetached): a reference slideAckedRemovedSegmentReferences
-// took off its segment's list for want of a segment to slide to
-// (mergeTree.ts:935-942, removeLocalRef keeps the segment): detached for
-// every read but mte_read_refs_transient, which still finds its segment.
-constexpr uint32_t kRefLive = 0x80000000u, kRefDetached = 0x40000000u, kRefOff = 0x20000000u;
-// a Transient reference (localReference.ts:263: never on its segment's list, so
-// nothing moves or slides it): kRefLive | kRefDetached | kRefTrans | its offset
-// in its segment, x = that segment's leaf id (mte_htree.h ht_ref_transient;
-// titems.c REF_TRANS): read as its segment's position + the offset, the offset
-// dropped once the segment is removed, -1 once the segment is gone
-constexpr uint32_t kRefTrans = 0x10000000u, kRefTransOff = 0x0fffffffu;
+// (the reference words kRefLive ... kRefTransOff: mte_passes.h)
 
 // a segment references may slide to (_getSlideToSegment, mergeTree.ts:893-913):
 // not a pending insert and not removed-and-acked (a pending removal is fine)

@@ -29,21 +29,14 @@
 // depth / next id / heap size in DocHdr pad0 / pad1.
 #pragma once
 
+#include "mte_passes.h"
 #include "mte_replay.h"
 
 namespace mte {
 
-constexpr int kTreeHeapCap = 255;  // entries per document (+ the unused index 0)
-constexpr uint32_t kHdrTreeEsc = 0x40000000u;  // tree pass: the document is TIER 1's (E = 4)
-constexpr uint32_t kHdrTreeBig = 0x20000000u;  // tree pass: the document is TIER 2's (E = 8, 16)
-constexpr uint32_t kHdrTreeHbmFlag = 0x10000000u;  // past TIER 2: the HBM tree pass (mte_htree.h kHdrTreeHbm)
-constexpr uint32_t kTH = 0x7u, kTCont = 0x8u, kTNsShift = 4, kTNs = 0x30u, kTPo = 0x40u, kTEmpty = 0x80u;
-constexpr uint32_t kTNl = 0x80000000u;
-constexpr uint16_t kRecNl = 0x8000u;  // op record flag (engine-internal): the insert's text holds a '\n'
 constexpr uint32_t kNsUndef = 0, kNsFalse = 1, kNsTrue = 2;
 constexpr int kMaxNodes = 8;       // MaxNodesInBlock, mergeTreeNodes.ts:373
 constexpr int32_t kTextGranularity = 256;  // textSegment.ts:19
-constexpr uint32_t kIdLimit = 1u << 23;
 
 // MTE_TREE_PROF (a profiling build only, `make prof`): with statistics on, the
 // tree pass's counters become phase clocks (s_memrealtime ticks, 100 MHz):
@@ -57,16 +50,6 @@ constexpr uint32_t kIdLimit = 1u << 23;
 #define TSTAT(...) MTE_STAT(__VA_ARGS__)
 #define TPROF(...)
 #endif
-
-struct TreeArgs {
-  uint32_t* tree;        // tree word of slot x of doc d: tree[d * cap + x]
-  uint2* heap;           // doc d: heap[d * (kTreeHeapCap + 1) + k], k = 1 .. size
-  const uint32_t* docs;  // the legacy documents
-  uint32_t n_docs;
-  const uint16_t* arena; // text (an append-merge looks at the last unit of a leaf)
-  uint32_t final_round;  // TIER 1: keep documents that shrink (no return to TIER 0)
-  uint32_t k_cap;        // this round's op cursor limit (TIER 0 / 1): documents advance together
-};
 
 __device__ __forceinline__ uint32_t t_h(uint32_t t) { return t & kTH; }
 __device__ __forceinline__ uint32_t t_ns(uint32_t t) { return (t & kTNs) >> kTNsShift; }
