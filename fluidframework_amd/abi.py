@@ -88,6 +88,23 @@ SEG_DTYPE = np.dtype([
     ("removers", "<u4"), ("client", "<i4"), ("kind", "<u4"), ("propset", "<u4")])
 assert SEG_DTYPE.itemsize == 32
 
+# mte_find_tiles: a query and its answer
+TILE_PRECEDING = 0x1
+TILE_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4"), ("key", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                             ("flags", "<u4")])
+assert TILE_QUERY_DTYPE.itemsize == 24
+TILE_HIT_DTYPE = np.dtype([("pos", "<i4"), ("status", "<i4"), ("ref_type", "<u4"), ("reserved", "<u4")])
+assert TILE_HIT_DTYPE.itemsize == 16
+
+
+class MteTileQuery(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("pos", C.c_int32), ("key", C.c_uint32), ("first", C.c_uint32),
+                ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MteTileHit(C.Structure):
+    _fields_ = [("pos", C.c_int32), ("status", C.c_int32), ("ref_type", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 class MteConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("n_keys", C.c_uint32),
@@ -132,7 +149,7 @@ EXPORTED_SYMBOLS = [
     "mte_digest_device", "mte_read_doc", "mte_read_segments", "mte_doc_status", "mte_stats_get", "mte_set_stats",
     "mte_comm_unique_id", "mte_comm_init", "mte_comm_share", "mte_comm_barrier", "mte_comm_allreduce_f64",
     "mte_comm_gather_digests", "mte_comm_world", "mte_comm_destroy", "mte_read_deltas", "mte_set_event_capacity",
-    "mte_set_ref_capacity", "mte_read_refs", "mte_read_refs_transient", "mte_read_ref_order",
+    "mte_set_ref_capacity", "mte_read_refs", "mte_read_refs_transient", "mte_read_ref_order", "mte_find_tiles",
 ]
 
 DOC_EVENTS = 0x8

@@ -684,6 +684,8 @@ struct mte_ctx {
   ncclComm_t comm = nullptr;  // cref->comm, or null
   int world = 1, rank = 0;
   DevBuf<uint64_t> d_comm;  // digests of all ranks / scalar reductions (sized exactly, comm_staging)
+  // mte_find_tiles: the call's queries + value ids, and its hits + property ids (words)
+  DevBuf<uint32_t> tile_in, tile_out;
   // per key, the largest property value id the context was given (load +
   // every batch) and whether any text segment or annotate ever carried it:
   // pass 1 packs the 4 property planes into one (kPack4) when every key's ids
@@ -1217,6 +1219,7 @@ int mte_destroy(mte_ctx* c) {
   comm_release(c);
   if (c->h_rcount) (void)hipHostFree(c->h_rcount);
   free_buf(c->d_comm);
+  free_buf(c->tile_in), free_buf(c->tile_out);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->tree_stream) (void)hipStreamDestroy(c->tree_stream);
@@ -2166,6 +2169,46 @@ int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
   }
   v->n_segs = m;
   v->n_text = nt;
+  return MTE_OK;
+}
+
+int mte_find_tiles(mte_ctx* c, const mte_tile_query* q, uint32_t n, const uint32_t* values, uint32_t n_values,
+                   mte_tile_hit* out, uint32_t* out_props) {
+  if (!c || (n && (!q || !out)) || (n_values && !values)) return MTE_E_INVALID_ARG;
+  JOIN_TAIL(c);
+  if (!n) return MTE_OK;
+  for (uint32_t i = 0; i < n; i++) {
+    const mte_tile_query& t = q[i];
+    if (t.doc >= c->docs.n_docs || t.pos < 0 || t.key >= c->n_keys || (uint64_t)t.first + t.count > n_values ||
+        (t.flags & ~MTE_TILE_PRECEDING))
+      return set_err(c, MTE_E_INVALID_ARG, "mte_find_tiles: query %u (doc %u, pos %d, key %u, values [%u, +%u), flags 0x%x)",
+                     i, t.doc, t.pos, t.key, t.first, t.count, t.flags);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  // one upload (queries, then the value ids), one launch, one download (hits, then the property ids)
+  static_assert(sizeof(mte_tile_query) == 24 && sizeof(mte_tile_hit) == 16, "mte_find_tiles packs these as words");
+  const uint64_t qw = 6ull * n, hw = 4ull * n, pw = out_props ? (uint64_t)n * c->n_keys : 0;
+  std::vector<uint32_t> in(qw + n_values), res(hw + pw);
+  std::memcpy(in.data(), q, qw * 4);
+  if (n_values) std::memcpy(in.data() + qw, values, 4ull * n_values);
+  if (int rc = grow(c, c->tile_in, in.size())) return rc;
+  if (int rc = grow(c, c->tile_out, res.size())) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->tile_in.p, in.data(), in.size() * 4, hipMemcpyHostToDevice, c->stream));
+  TileArgs a;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
+  a.cap = c->cap;
+  a.n_keys = c->n_keys;
+  a.n = n;
+  a.q = (const mte_tile_query*)c->tile_in.p;
+  a.values = c->tile_in.p + qw;
+  a.out = (mte_tile_hit*)c->tile_out.p;
+  a.out_props = out_props ? c->tile_out.p + hw : nullptr;
+  HIPCHK(c, launch_find_tiles(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res.data(), c->tile_out.p, res.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(out, res.data(), hw * 4);
+  if (out_props && pw) std::memcpy(out_props, res.data() + hw, pw * 4);
   return MTE_OK;
 }
 

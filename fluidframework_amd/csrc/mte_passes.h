@@ -4,7 +4,8 @@
 // (mte_pass_tree.hip, mte_pass_htree.hip, mte_pass_flat.hip,
 // mte_pass_chunk.hip) so the passes compile in parallel and one can be rebuilt
 // alone; mte_engine.hip drives them (launch_replay) and includes no kernel
-// header.  The pass headers include this one for the declarations below.
+// header.  The pass headers include this one for the declarations below.  The
+// batched read-only queries (mte_query.h, mte_query.hip) follow the same rule.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -186,5 +187,19 @@ hipError_t launch_round_plan(const ReplayArgs& a, const ChunkArgs& ch, const Rou
 template <int K>
 hipError_t launch_round_run(const ReplayArgs& a, const ChunkArgs& ch, const RoundArgs& rd, uint32_t n_docs,
                             hipStream_t s);
+
+// ---- batched queries (mte_query.h) ------------------------------------------
+struct TileArgs {
+  const DocHdr* hdr;
+  SegSoA soa;
+  uint32_t cap;
+  uint32_t n_keys;
+  uint32_t n;                  // queries; one wave each
+  const mte_tile_query* q;     // validated by the host (doc, key, first + count)
+  const uint32_t* values;
+  mte_tile_hit* out;           // [n]
+  uint32_t* out_props;         // [n][n_keys], or null
+};
+hipError_t launch_find_tiles(const TileArgs& a, hipStream_t s);
 
 }  // namespace mte

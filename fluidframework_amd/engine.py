@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _native
 from .abi import (DELTA_DTYPE, DOC_INIT_DTYPE, EXPORTED_SYMBOLS, OP_DTYPE, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE,
+                  TILE_HIT_DTYPE, TILE_PRECEDING, TILE_QUERY_DTYPE,
                   MergeTreeError, MteBatch, MteConfig, MteDocView, MteSegList, MteStats, ptr)
 from .packing import units_to_str
 
@@ -235,6 +236,45 @@ class DeviceEngine(EngineBase):
     def digest_device(self, device_ptr):
         self._check(self.lib.mte_digest_device(self.ctx, C.c_void_p(device_ptr), self.n_docs),
                     "digest_device")
+
+    def find_tiles_raw(self, q, values, want_props=True):
+        """mte_find_tiles over TILE_QUERY_DTYPE[n] and the value ids its queries'
+        (first, count) slices index -> (TILE_HIT_DTYPE[n], uint32[n, n_keys] or
+        None): every query answered by one device call."""
+        q = _arr(q, TILE_QUERY_DTYPE)
+        values = _arr(values, np.uint32)
+        hits = np.zeros(len(q), TILE_HIT_DTYPE)
+        props = np.zeros((len(q), self.n_keys), np.uint32) if want_props else None
+        self._check(self.lib.mte_find_tiles(self.ctx, ptr(q), len(q), ptr(values), len(values), ptr(hits),
+                                            ptr(props)), "find_tiles")
+        return hits, props
+
+    def find_tiles(self, queries, interner):
+        """SharedString.findTile for many documents at once (include/mte.h
+        mte_find_tiles): queries = [(doc, start_pos, label, preceding)], labels
+        looked up in `interner` (packing.Interner.tile_values) ->
+        [None | {"pos", "refType", "props"}], one device call for all of them.
+        Raises MergeTreeError for a document whose status is not OK.  One
+        wavefront walks each queried document: fine for many ordinary documents,
+        slow for a document of a million segments."""
+        q = np.zeros(len(queries), TILE_QUERY_DTYPE)
+        values, where = [], {}
+        for i, (doc, pos, label, preceding) in enumerate(queries):
+            if label not in where:
+                key, ids = interner.tile_values(label)
+                where[label] = (key or 0, len(values), len(ids))
+                values.extend(ids)
+            q[i] = (doc, pos, *where[label], TILE_PRECEDING if preceding else 0)
+        if self.n_keys == 0:  # no property plane: no marker carries a label
+            return [None] * len(queries)
+        hits, props = self.find_tiles_raw(q, values)
+        out = []
+        for i, h in enumerate(hits):
+            if h["status"] != 0:
+                raise MergeTreeError(int(h["status"]), f"find_tiles: document {int(q[i]['doc'])}")
+            out.append(None if h["pos"] < 0 else
+                       {"pos": int(h["pos"]), "refType": int(h["ref_type"]), "props": interner.decode_props(props[i])})
+        return out
 
     def _read_doc(self, doc, vptr):
         return self.lib.mte_read_doc(self.ctx, doc, vptr)

@@ -141,6 +141,26 @@ export interface EngineStats {
   algoBytes: number;
 }
 
+/** A marker findTile found: its refType, its properties and its markerId. */
+export interface TileMarker {
+  refType: number;
+  properties: PropertySet | undefined;
+  getId(): string | undefined;
+}
+export interface TileQuery {
+  client: BatchClient;
+  /** default 0 */
+  startPos?: number;
+  tileLabel: string;
+  /** default true */
+  preceding?: boolean;
+}
+export interface TileResult {
+  tile: TileMarker;
+  /** the marker's position in the client's own view */
+  pos: number;
+}
+
 export class MergeTreeEngine {
   constructor(options?: EngineOptions);
   readonly nKeys: number;
@@ -152,6 +172,9 @@ export class MergeTreeEngine {
   sync(): void;
   /** Delta-event records per op record of {events: true} documents (mte_set_event_capacity). */
   setEventCapacity(perOp: number): void;
+  /** SharedString.findTile for many documents: one flush, one sync and one
+   *  device call (mte_find_tiles) for the whole array, any document order. */
+  findTiles(queries: TileQuery[]): (TileResult | undefined)[];
   digests(): BigUint64Array;
   statuses(): Int32Array;
   stats(): EngineStats;
@@ -327,6 +350,12 @@ export class BatchClient {
   flush(): void;
   /** TestClient.getText(start?, end?): markers count one position, contribute no text. */
   getText(start?: number, end?: number): string;
+  /** getText with one space per visible marker, so positions index into the string. */
+  getTextWithPlaceholders(start?: number, end?: number): string;
+  /** Client.findTile: the nearest visible Tile marker labelled tileLabel at or
+   *  before startPos (preceding, the default) or at or after it; following at
+   *  startPos >= length finds nothing. */
+  findTile(startPos: number | undefined, tileLabel: string, preceding?: boolean): TileResult | undefined;
   getLength(): number;
   getCurrentSeq(): number;
   getCollabWindow(): { clientId: number; currentSeq: number; minSeq: number; collaborating: boolean };

@@ -29,6 +29,7 @@ const packing = require("./packing");
 const { IntervalCollection, IntervalType, RefType } = require("./intervals");
 
 const { BatchBuilder, DocClients, Interner, MergeTreeError, packDocInits, packSegments, utf16 } = packing;
+const MARKER_ID_KEY = "markerId";  // reservedMarkerIdKey (mergeTreeNodes.ts)
 
 // UTF-16 code units -> JS string (chunked: apply() on a huge array overflows the stack)
 function unitsToString(u) {
@@ -317,6 +318,48 @@ class MergeTreeEngine {
       this.unitViews[doc] = v;
     }
     return v;
+  }
+
+  /** SharedString.findTile for many documents at once (mte_find_tiles): one
+   *  flush, one sync and one device call for the whole array, in any document
+   *  order.  -> per query {tile: {refType, properties, getId()}, pos} | undefined.
+   *  Throws for a document whose status is not OK.  One wavefront walks each
+   *  queried document: slow over a document of a million segments.
+   *  @param {{client: BatchClient, startPos: number, tileLabel: string, preceding?: boolean}[]} queries */
+  findTiles(queries) {
+    this.flush();
+    this.sync();
+    const n = queries.length;
+    const q = new Uint32Array(6 * n), values = [], where = new Map();
+    for (let i = 0; i < n; i++) {
+      const t = queries[i];
+      if (!(t.client instanceof BatchClient) || t.client.engine !== this) {
+        throw new MergeTreeError(-1, "findTiles: query " + i + " is not for a client of this engine");
+      }
+      const pos = t.startPos === undefined ? 0 : t.startPos;
+      if (!Number.isInteger(pos) || pos < 0 || pos > 0x7fffffff) {
+        throw new MergeTreeError(-1, "findTiles: query " + i + ": startPos " + pos);
+      }
+      let w = where.get(t.tileLabel);
+      if (w === undefined) {
+        const [k, ids] = this.interner.tileValues(t.tileLabel);
+        w = [k === null ? 0 : k, values.length, ids.length];
+        for (const id of ids) values.push(id);
+        where.set(t.tileLabel, w);
+      }
+      q.set([t.client.doc, pos, w[0], w[1], w[2], t.preceding === false ? 0 : 1], 6 * i);
+    }
+    if (n === 0 || this.nKeys === 0) return new Array(n).fill(undefined);
+    const r = this.addon.findTiles(this.ctx, q, Uint32Array.from(values), this.nKeys);
+    const out = new Array(n).fill(undefined);  // no holes: forEach / map visit every answer
+    for (let i = 0; i < n; i++) {
+      if (r.hits[4 * i + 1] !== 0) throw docError(r.hits[4 * i + 1], queries[i].client.doc);
+      if (r.hits[4 * i] < 0) continue;
+      const properties = this.interner.decode(r.props.subarray(i * this.nKeys, (i + 1) * this.nKeys));
+      out[i] = { tile: { refType: r.hits[4 * i + 2], properties,
+        getId() { return properties === undefined ? undefined : properties[MARKER_ID_KEY]; } }, pos: r.hits[4 * i] };
+    }
+    return out;
   }
 
   /** Per-doc canonical digests (4 x u64 each, DESIGN.md "Digest"). */
@@ -1000,6 +1043,38 @@ class BatchClient {
       p += len;
     }
     return out;
+  }
+
+  /** MergeTreeTextHelper.getText with placeholder " " (MergeTreeTextHelper.ts:49-74;
+   *  SharedString.getTextWithPlaceholders): as getText, every visible marker
+   *  contributing one space, so positions (findTile's) index into the string. */
+  getTextWithPlaceholders(start, end) {
+    const v = this.engine._view(this.doc);
+    const s0 = start === undefined ? 0 : start;
+    const e0 = end === undefined ? v.length : end;
+    let out = "";
+    let p = 0, t = 0;
+    for (let i = 0; i < v.segLen.length && p < e0; i++) {
+      const len = v.segLen[i];
+      if (v.segKind[i] === 0) {
+        if (p + len > s0) out += v.text.substring(t + Math.max(s0 - p, 0), t + Math.min(e0 - p, len));
+        t += len;
+      } else if (p + len > s0) {
+        out += " ".repeat(Math.min(e0 - p, len) - Math.max(s0 - p, 0));
+      }
+      p += len;
+    }
+    return out;
+  }
+
+  /** Client.findTile (client.ts:1185-1188 -> MergeTree.findTile,
+   *  mergeTree.ts:1135-1163): the nearest visible Tile marker whose
+   *  referenceTileLabels holds tileLabel, at or before startPos (preceding, the
+   *  default) or at or after it -> {tile: {refType, properties, getId()}, pos} |
+   *  undefined.  Following at startPos >= length finds nothing (DESIGN.md).  One
+   *  device call; MergeTreeEngine.findTiles asks many documents in one. */
+  findTile(startPos, tileLabel, preceding = true) {
+    return this.engine.findTiles([{ client: this, startPos, tileLabel, preceding }])[0];
   }
 
   getLength() {

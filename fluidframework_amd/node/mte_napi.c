@@ -655,6 +655,50 @@ static napi_value js_read_ref_order(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* findTiles(ctx, queries, values, nKeys) -> {hits Int32Array(4n) (mte_tile_hit: pos,
+   status, refType, 0), props Uint32Array(n * nKeys)}: mte_find_tiles over
+   queries = Uint32Array(6n) (mte_tile_query: doc, pos, key, first, count,
+   flags) and the value ids their (first, count) slices index.  The symbol is
+   weak: an engine library without it (the CPU restatement the tests link this
+   file against) loads, and findTiles throws code MTE_E_UNSUPPORTED. */
+extern __typeof__(mte_find_tiles) mte_find_tiles __attribute__((weak));
+
+static napi_value js_find_tiles(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return NULL;
+  ctx_box* box = get_box(env, argv[0]);
+  if (!box) return NULL;
+  void *q = NULL, *vals = NULL;
+  size_t qb = 0, vb = 0;
+  uint32_t nk = 0;
+  if (!get_bytes(env, argv[1], &q, &qb) || !get_bytes(env, argv[2], &vals, &vb)) return NULL;
+  NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &nk));
+  if (!check_nkeys(env, box, nk)) return NULL;
+  if (!mte_find_tiles) {
+    throw_rc(env, MTE_E_UNSUPPORTED, NULL, "findTiles: this engine library has no mte_find_tiles");
+    return NULL;
+  }
+  if (qb % sizeof(mte_tile_query) || vb % 4 || qb / sizeof(mte_tile_query) > 0xffffffffu || vb / 4 > 0xffffffffu) {
+    throw_rc(env, MTE_E_INVALID_ARG, box->ctx, "findTiles: buffer sizes");
+    return NULL;
+  }
+  const size_t n = qb / sizeof(mte_tile_query);
+  napi_value o, ab_h, ab_p, th, tp;
+  void *ph = NULL, *pp = NULL;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(mte_tile_hit), &ph, &ab_h));
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * nk * 4, &pp, &ab_p));
+  if (throw_rc(env, mte_find_tiles(box->ctx, (const mte_tile_query*)q, (uint32_t)n, (const uint32_t*)vals,
+                                   (uint32_t)(vb / 4), (mte_tile_hit*)ph, n && nk ? (uint32_t*)pp : NULL),
+               box->ctx, "mte_find_tiles"))
+    return NULL;
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n * 4, ab_h, 0, &th));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n * nk, ab_p, 0, &tp));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "hits", th);
+  napi_set_named_property(env, o, "props", tp);
+  return o;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   const napi_property_descriptor d[] = {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -685,6 +729,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"setRefCapacity", NULL, js_set_ref_capacity, NULL, NULL, NULL, napi_enumerable, NULL},
       {"readRefs", NULL, js_read_refs, NULL, NULL, NULL, napi_enumerable, NULL},
       {"readRefOrder", NULL, js_read_ref_order, NULL, NULL, NULL, napi_enumerable, NULL},
+      /* not enumerable: Object.keys() of the addon stays the list of functions
+         every engine library serves; findTiles depends on the library (above) */
+      {"findTiles", NULL, js_find_tiles, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

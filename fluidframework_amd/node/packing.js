@@ -34,6 +34,7 @@ const OP_REF = 8;            // MTE_OP_REF: create / remove a local reference
 const OP_RELPOS = 9;         // MTE_OP_RELPOS: relative positions of the record that follows
 const RP_POS1 = 0x100, RP_BEFORE1 = 0x200, RP_POS2 = 0x400, RP_BEFORE2 = 0x800;
 const MARKER_ID_KEY = "markerId";  // reservedMarkerIdKey (mergeTreeNodes.ts)
+const TILE_LABELS_KEY = "referenceTileLabels";  // reservedTileLabelsKey (referencePositions.ts)
 const REF_SLIDE_ON_REMOVE = 0x40, REF_STAY_ON_REMOVE = 0x80, REF_TRANSIENT = 0x100;  // ReferenceType (ops.ts)
 const DELTA_REGEN = 0x10;    // MTE_DELTA_REGEN: kind flag of a regenerated op's records
 const ANNOTATE_SLOTS = 32;   // MTE_ANNOTATE_SLOTS: pending local annotate groups tracked per document
@@ -182,6 +183,21 @@ class Interner {
       this.valueJson.push(cj);
     }
     return i;
+  }
+  /** [plane of "referenceTileLabels" or null, the ids of its noted values whose
+   *  array holds `label`]: a label as mte_find_tiles takes it (refHasTileLabel,
+   *  referencePositions.ts:20-37; packing.py Interner.tile_values).  Interns
+   *  nothing: nKeys is a hard limit. */
+  tileValues(label) {
+    const k = this.keys.get(TILE_LABELS_KEY);
+    if (k === undefined) return [null, []];
+    const out = [], b = 1 << k, M = this.keyMask;
+    for (let x = 1; x < this.valueJson.length && x < M.length; x++) {
+      if (!(M[x] & b) || this.valueJson[x] === "NaN") continue;
+      const v = JSON.parse(this.valueJson[x]);
+      if (Array.isArray(v) && v.includes(label)) out.push(x);
+    }
+    return [k, out];
   }
   /** canonical JSON of a value id */
   jsonOf(id) {

@@ -41,6 +41,7 @@ from .abi import (COMBINE_PAIR, MTE_VALUE_UNEQUAL, F_COMBINE, F_LOCAL, F_REGENER
 INSERT, REMOVE, ANNOTATE, GROUP = 0, 1, 2, 3  # MergeTreeDeltaType, ops.ts:43-48
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 MARKER_ID_KEY = "markerId"  # reservedMarkerIdKey (mergeTreeNodes.ts)
+TILE_LABELS_KEY = "referenceTileLabels"  # reservedTileLabelsKey (referencePositions.ts)
 
 
 def canonical_json(v) -> str:
@@ -123,6 +124,22 @@ class Interner:
             self.values[cj] = i
             self.value_json.append(cj)
         return i
+
+    def tile_values(self, label: str):
+        """-> (plane of "referenceTileLabels", the ids of its noted values whose
+        array holds `label`): a label as mte_find_tiles takes it (refHasTileLabel,
+        referencePositions.ts:20-37).  (None, []) when no segment was ever given
+        the key.  Interns nothing: n_keys is a hard limit."""
+        k = self.keys.get(TILE_LABELS_KEY)
+        if k is None:
+            return None, []
+        out = []
+        for x in range(1, min(len(self.value_json), len(self.key_mask))):
+            if self.key_mask[x] & (1 << k):
+                v = json.loads(self.value_json[x]) if self.value_json[x] != "NaN" else None
+                if isinstance(v, list) and label in v:
+                    out.append(x)
+        return k, out
 
     def json_of(self, vid: int) -> str:
         """canonical JSON of a value id"""

@@ -615,6 +615,51 @@ typedef struct mte_seg_list {
   uint64_t n_text;
 } mte_seg_list;
 int mte_read_segments(mte_ctx* ctx, uint32_t doc, mte_seg_list* list);
+
+/* ---- Batched marker search: SharedString.findTile for many documents ------
+ * Each query asks one document for the nearest marker whose refType has the
+ * ReferenceType.Tile bit and whose "referenceTileLabels" array holds a label,
+ * before (MTE_TILE_PRECEDING) or after a position of the document's own view
+ * (MergeTree.findTile, mergeTree.ts:1135-1163; refHasTileLabel,
+ * referencePositions.ts:20-37):
+ *   preceding: the last such marker at a position <= pos (every pos >= length
+ *              gives the document's last one);
+ *   following: the first such marker at a position >= pos, for pos < length;
+ *              nothing at pos >= length (at pos == length the reference's walk
+ *              may return a removed marker; the engine does not).
+ * Only visible segments count: a local client's pending inserts do, its
+ * pending removals do not.  The label is given as value ids: `key` is the
+ * property plane of "referenceTileLabels" and values[first .. first + count)
+ * are the ids of that key's values whose array holds the label (the host's
+ * interner picks them; count == 0 finds nothing).
+ *
+ * All n queries are answered on the device by one upload, one kernel launch
+ * (one wavefront per query) and one download, in any document order, with
+ * repeats; n == 0 launches nothing.  MTE_E_INVALID_ARG, before any launch, for
+ * doc >= n_docs, pos < 0, key >= n_keys, first + count > n_values or an
+ * unknown flag.  out[i].pos is the marker's own-view position (-1: none; a
+ * document whose status is not MTE_OK answers -1 with its status);
+ * out_props, when given, receives the marker's n_keys value ids per query
+ * (zeros without a hit).  One wavefront walks a whole document, so a query
+ * over a document of a million segments is slow (no tile-parallel variant
+ * exists yet).                                                              */
+#define MTE_TILE_PRECEDING 0x1u
+typedef struct mte_tile_query {
+  uint32_t doc;
+  int32_t pos;           /* startPos, >= 0 */
+  uint32_t key;          /* props plane of "referenceTileLabels" */
+  uint32_t first, count; /* values[first .. first + count) */
+  uint32_t flags;        /* MTE_TILE_PRECEDING or 0 */
+} mte_tile_query;
+typedef struct mte_tile_hit {
+  int32_t pos;           /* own-view position of the marker; -1: none */
+  int32_t status;        /* the document's status */
+  uint32_t ref_type;     /* the marker's refType */
+  uint32_t reserved;
+} mte_tile_hit;
+int mte_find_tiles(mte_ctx* ctx, const mte_tile_query* q, uint32_t n, const uint32_t* values, uint32_t n_values,
+                   mte_tile_hit* out, uint32_t* out_props);
+
 int mte_doc_status(mte_ctx* ctx, int32_t* out, uint32_t n_docs);
 int mte_stats_get(mte_ctx* ctx, mte_stats* out);
 /* Statistics accounting (the counters of mte_stats, like the reference's
