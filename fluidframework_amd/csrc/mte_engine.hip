@@ -213,12 +213,22 @@ __global__ void image_kernel(SegSoA soa, uint32_t cap, uint32_t n_planes, const 
 // kernels fetch with one scalar load (mte_kernels.h): the first two entries
 // inlined, the count of keys < n_keys.  One thread per set; runs at the start
 // of every mte_run (inside the timed region).
+//
+// pack (pass 1 will hold the four planes as one packed register, kPack4): the
+// record's second half is the whole set folded, in entry order, into what it
+// does to the packed plane -- plane' = (plane & keep) | val -- and the side
+// key's value.  Each entry is set_plane's old byte update, (x & ~m) | (v << sh)
+// with v unmasked (the host packs only when every id that reaches a byte is
+// < 256), and the composition of such updates is again one: a later entry of
+// a key clears the earlier one's byte, value 0 leaves byte 0, keys >= n_keys
+// and the side key never reach the bytes.
 __global__ void props_kernel(const mte_propset* __restrict__ ps, uint32_t n_ps, const mte_prop* __restrict__ pe,
-                             uint32_t n_keys, uint4* __restrict__ cps) {
+                             uint32_t n_keys, uint32_t side_key, bool pack, uint4* __restrict__ cps) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_ps) return;
   const mte_propset s = ps[i];
   uint32_t k0 = kNoKey, k1 = kNoKey, v0 = 0, v1 = 0, nw = 0;
+  uint32_t keep = ~0u, val = 0, side = 0, has_side = 0;
   for (uint32_t t = 0; t < s.count; t++) {
     const mte_prop p = pe[s.first + t];
     const bool ok = p.key < n_keys;
@@ -230,9 +240,19 @@ __global__ void props_kernel(const mte_propset* __restrict__ ps, uint32_t n_ps, 
       k1 = ok ? p.key : kNoKey;
       v1 = p.value;
     }
+    if (pack && ok && p.key < 4u) {
+      if (p.key == side_key) {
+        side = p.value;
+        has_side = 1;
+      } else {
+        const uint32_t sh = p.key * 8u, m = 0xffu << sh;
+        keep &= ~m;
+        val = (val & ~m) | (p.value << sh);
+      }
+    }
   }
   cps[2 * i] = make_uint4(k0 | (k1 << 8) | ((s.count > 2 ? 1u : 0u) << 16), v0, v1, nw);
-  cps[2 * i + 1] = make_uint4(0, 0, 0, 0);
+  cps[2 * i + 1] = pack ? make_uint4(keep, val, side, has_side) : make_uint4(0, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -876,6 +896,23 @@ int round_phase_loop(mte_ctx* c, const ReplayArgs& a, size_t lds) {
   return MTE_OK;
 }
 
+// Whether pass 1 holds the four property planes as one packed register plane
+// (kPack4): 4 keys at most and every value id the context was ever given fits
+// a byte, or all but one side key that only marker inserts ever set (*side,
+// else kNoKey).  props_kernel compiles the batch's sets for the same answer.
+bool pass1_packs(const mte_ctx* c, uint32_t* side) {
+  *side = kNoKey;
+  bool pack = c->kt == 4 && c->pack_props;
+  for (uint32_t k = 0; k < 4 && pack; k++) {
+    if (c->max_vid_k[k] < 256) continue;
+    if (*side == kNoKey && !c->key_text[k]) *side = k;  // set on markers only
+    else pack = false;
+  }
+  for (uint32_t k = 4; k < MTE_MAX_KEYS; k++) pack = pack && c->max_vid_k[k] == 0;  // kt = 4: 4 keys at most
+  if (!pack) *side = kNoKey;
+  return pack;
+}
+
 template <int K, bool S>
 int launch_replay(mte_ctx* c, const ReplayArgs& a) {
   const BatchSlot& sl = c->slot[c->rslot];
@@ -925,14 +962,8 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
   // ever given), pass 1 holds the four planes as one packed register plane
   if (b1) {
     if constexpr (K == 4) {
-      uint32_t side = kNoKey;
-      bool pack = c->pack_props;
-      for (uint32_t k = 0; k < 4 && pack; k++) {
-        if (c->max_vid_k[k] < 256) continue;
-        if (side == kNoKey && !c->key_text[k]) side = k;  // set on markers only
-        else pack = false;
-      }
-      for (uint32_t k = 4; k < MTE_MAX_KEYS; k++) pack = pack && c->max_vid_k[k] == 0;  // kt = 4: 4 keys at most
+      uint32_t side;
+      const bool pack = pass1_packs(c, &side);
       ReplayArgs ap = a;
       ap.side_key = side;
       if (pack) HIPCHK(c, (launch_pair<kPack4, S>(ap, b1, c->stream)));
@@ -1772,8 +1803,10 @@ int mte_run(mte_ctx* c) {
     HIPCHK(c, hipGetLastError());
   }
   if (s.n_propsets) {
+    uint32_t side;
+    const bool pack = pass1_packs(c, &side);
     hipLaunchKernelGGL(props_kernel, dim3((uint32_t)((s.n_propsets + 255) / 256)), dim3(256), 0, c->stream, s.ps.p,
-                       (uint32_t)s.n_propsets, s.pe.p, c->n_keys, s.cps.p);
+                       (uint32_t)s.n_propsets, s.pe.p, c->n_keys, side, pack, s.cps.p);
     HIPCHK(c, hipGetLastError());
   }
   int rc;

@@ -75,7 +75,12 @@ struct SegSoA {
 // in place: w0 seq | w1 ref_seq | w2 min_seq | w3 type | client << 8 | flags << 16
 // | w4 pos1 | w5 pos2 | w6 a | w7 b (include/mte.h).  Property sets are compiled
 // per run into 32-B records (props_kernel): w0 k0 | k1 << 8 | (count > 2) << 16
-// (key 0xff = none) | w1 v0 | w2 v1 | w3 keys < n_keys in the set | w4-7 0.
+// (key 0xff = none) | w1 v0 | w2 v1 | w3 keys < n_keys in the set.  Every pass
+// reads w0-w3.  When pass 1 packs the four planes into one (kPack4, below) the
+// second half holds the whole set folded for that plane, which only the kPack4
+// step reads: w4 keep (the plane's bytes the set leaves alone) | w5 val (the
+// packed bytes it sets: plane' = (plane & keep) | val) | w6 the side key's
+// value | w7 1 if the set has one.  Otherwise w4-7 are 0.
 constexpr uint32_t kNoKey = 0xffu;
 constexpr uint32_t kRecPad = 512;  // zeroed records after the last op (L2 prefetch runs ahead)
 

@@ -9,11 +9,14 @@
 //                  (<= 1022 segments), for documents pass 1 escalated.
 //   stream_kernel — pass 3 (mte_stream.h): larger documents, HBM-resident.
 //
-// Both run the same per-op step (doc_step) on a register-resident document.
-// Op records (64 B compiled records, mte_kernels.h) are read with scalar
-// loads straight into SGPRs (the op index is wave-uniform): the next op's
-// first 32 bytes are in flight while the current op runs, and every 64 ops a
-// vector load touches the next 64 records so the scalar loads hit L2.
+// The tiers E >= 8 run the per-op step doc_step on a register-resident
+// document: op records (32 B, mte_kernels.h) are read with scalar loads
+// straight into SGPRs (the op index is wave-uniform), the next op's record in
+// flight while the current op runs, and a vector load touches the records
+// ahead so the scalar loads hit L2.  The pass-1 tiers run the per-slot-flag
+// step (mte_step1.h): E <= 2 takes its records 64 at a time, one per lane,
+// and decodes and window-checks them vector-wide (block_run); E = 4 fetches
+// each op's record with a vector load (doc_step_v).
 #pragma once
 
 #include <type_traits>
@@ -94,13 +97,6 @@ __device__ __forceinline__ void set_one_plane(uint32_t (&p)[E], const bool (&sel
 template <int E, int K>
 __device__ __forceinline__ void set_plane(uint32_t (&pr)[kRP<K>][E], const bool (&sel)[E], uint32_t key,
                                           uint32_t val) {
-  if constexpr (K == kPack4) {
-    // byte `key` of the packed plane (key < 4 and val < 256: the host's choice)
-    const uint32_t sh = key * 8u, keep = ~(0xffu << sh), v = val << sh;
-#pragma unroll
-    for (int jj = 0; jj < E; jj++) pr[0][jj] = sel[jj] ? ((pr[0][jj] & keep) | v) : pr[0][jj];
-    return;
-  }
   // `key` is wave-uniform: one scalar branch picks the plane, so only that
   // plane's E selects issue (a branch-free form costs K x E selects, and a
   // `kk == key` test per plane gets folded into pr[key], a dynamic index that
@@ -121,16 +117,17 @@ __device__ __forceinline__ void set_plane(uint32_t (&pr)[kRP<K>][E], const bool 
 template <int E, int K>
 __device__ __forceinline__ void apply_props(uint32_t (&pr)[kRP<K>][E], const bool (&sel)[E], uint32_t pk,
                                             uint32_t v0, uint32_t v1, uint32_t psi, const ReplayArgs& a) {
+  // the packed plane takes the whole set as one (keep, val) pair, folded by
+  // props_kernel (seg_op_v, put_new_v)
+  static_assert(K != kPack4, "kPack4 applies the compiled (keep, val) pair");
   const uint32_t k0 = pk & 0xffu, k1 = (pk >> 8) & 0xffu;
-  // kPack4: the side key never goes into the packed bytes (ReplayArgs::side_key)
-  const uint32_t skip = K == kPack4 ? a.side_key : kNoKey;
-  if (k0 != kNoKey && k0 != skip) set_plane<E, K>(pr, sel, k0, v0);
-  if (k1 != kNoKey && k1 != skip) set_plane<E, K>(pr, sel, k1, v1);
+  if (k0 != kNoKey) set_plane<E, K>(pr, sel, k0, v0);
+  if (k1 != kNoKey) set_plane<E, K>(pr, sel, k1, v1);
   if (pk >> 16) {
     const mte_propset ps = a.ps[psi];
     for (uint32_t t = 2; t < ps.count; t++) {
       const mte_prop p = a.pe[ps.first + t];
-      if (p.key < a.n_keys && p.key != skip) set_plane<E, K>(pr, sel, uni(p.key), uni(p.value));
+      if (p.key < a.n_keys) set_plane<E, K>(pr, sel, uni(p.key), uni(p.value));
     }
   }
 }
@@ -686,8 +683,10 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   s8v cur;
   uint32_t vcur;
   [[maybe_unused]] const uint32_t* vrec = nullptr;  // this lane's dword of the record in vcur
-  if constexpr (E <= kStepVEmax) {
-    // the pass-1 tiers read op records through a vector load: dword i in lane
+  if constexpr (E <= kBlockEmax) {
+    // block decode (mte_step1.h): the records come 64 at a time, in block_run
+  } else if constexpr (E <= kStepVEmax) {
+    // the E = 4 tier reads op records through a vector load: dword i in lane
     // i < 8.  Its wait is on vmcnt, so the LDS traffic of an op (shift
     // permutes, zamboni) never waits for the next record as it does for a
     // scalar load in flight (SMEM and LDS share lgkmcnt, and SMEM returns out
@@ -706,19 +705,28 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   const bool per_burst = limit <= kTouchSpan / 2;
   if (per_burst) touch_records(D, D.k == 0 ? 0u : D.k + limit, pending, sink);
   else touch_records(D, D.k + 16, pending, sink);
-  for (;;) {
-    if (!per_burst && (D.k & (kTouchSpan / 2 - 1)) == 0) touch_records(D, D.k + kTouchSpan / 2, pending, sink);
-    int rc;
-    if constexpr (E <= kStepVEmax) rc = doc_step_v<E, K, S>(R, D, st, vcur, vrec, a, zlds, emin);
-    else rc = doc_step<E, K, S>(R, D, st, cur, a, zlds, emin);
-    if (rc != 0) {
-      if (rc < 0) {
-        D.status = rc;
-        D.running = false;
-      }
-      break;
+  if constexpr (E <= kBlockEmax) {
+    // these tiers only run pass 1's short bursts, touched ahead once (above)
+    const int rc = block_run<E, K, S>(R, D, st, a, zlds, emin, kend);
+    if (rc < 0) {
+      D.status = rc;
+      D.running = false;
     }
-    if (D.k >= kend) break;
+  } else {
+    for (;;) {
+      if (!per_burst && (D.k & (kTouchSpan / 2 - 1)) == 0) touch_records(D, D.k + kTouchSpan / 2, pending, sink);
+      int rc;
+      if constexpr (E <= kStepVEmax) rc = doc_step_v<E, K, S>(R, D, st, vcur, vrec, a, zlds, emin);
+      else rc = doc_step<E, K, S>(R, D, st, cur, a, zlds, emin);
+      if (rc != 0) {
+        if (rc < 0) {
+          D.status = rc;
+          D.running = false;
+        }
+        break;
+      }
+      if (D.k >= kend) break;
+    }
   }
   if (D.k >= D.k1) D.running = false;
   store_regs<E, K>(R, D, a);

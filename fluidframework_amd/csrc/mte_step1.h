@@ -9,8 +9,17 @@
 // its own lane's earlier slots, "I am right after it" from its neighbour's
 // flag, and every piece of a split leaf is rebuilt from the values the slot
 // pulled in the shift.  The scalar unit — one per CU, shared by four SIMDs —
-// then only decodes the op, branches on the op type and on "is there a
-// split", and keeps the collab window; the rest is VALU work on each SIMD.
+// then only decodes the op and branches on the op type and on "is there a
+// split"; the rest is VALU work on each SIMD.
+//
+// What depends on the records alone is done 64 records at a time (block_run,
+// the tiers E <= kBlockEmax): lane i loads record D.k + i whole, the wave
+// decodes it, checks client and type and runs the whole collab window as a
+// prefix computation (running maxima of the ENDs' seq and min_seq), and the op
+// loop reads a record with v_readlane at a scalar lane index and tests one bit
+// for "minSeq advances here".  E = 4 keeps the per-op fetch and window of
+// doc_step_v.  On the kPack4 layout a property set is applied as the (keep,
+// val) pair props_kernel folded it into (mte_kernels.h), whatever its size.
 #pragma once
 
 #include "mte_kernels.h"
@@ -185,23 +194,15 @@ __device__ __forceinline__ void put_new_v(Regs<E, K>& R, uint32_t atw, const s8v
   for (int kk = 0; kk < kRP<K>; kk++) pr[kk][0] = 0;
   if (kKeys<K> > 0 && psi != MTE_NO_PROPS) {
     const s8v q2 = sload_props(a, psi);
-    apply_props<1, K>(pr, one, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
-    MTE_STAT(st[kStPwrites] += (uint32_t)q2[3];)
     if constexpr (K == kPack4) {
-      // a marker's side-key value goes to its toff register (ReplayArgs::side_key)
-      if (marker && a.side_key < 4u) {
-        const uint32_t pk = (uint32_t)q2[0];
-        if ((pk & 0xffu) == a.side_key) toff = (uint32_t)q2[1];
-        if (((pk >> 8) & 0xffu) == a.side_key) toff = (uint32_t)q2[2];
-        if (pk >> 16) {
-          const mte_propset ps = a.ps[psi];
-          for (uint32_t t = 2; t < ps.count; t++) {
-            const mte_prop p = a.pe[ps.first + t];
-            if (p.key == a.side_key) toff = uni(p.value);
-          }
-        }
-      }
+      // the set folded by props_kernel: the packed bytes, and a marker's
+      // side-key value, which goes to its toff register (ReplayArgs::side_key)
+      pr[0][0] = (uint32_t)q2[5];
+      toff = (marker && q2[7]) ? (uint32_t)q2[6] : toff;
+    } else {
+      apply_props<1, K>(pr, one, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
     }
+    MTE_STAT(st[kStPwrites] += (uint32_t)q2[3];)
   }
   MTE_STAT(if (!marker) st[kStUnits] += (uint32_t)pos2;)
   bool at[E];
@@ -408,28 +409,71 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
         // PropertiesManager.addProperties (segmentPropertiesManager.ts:63-151)
         const uint32_t psi = (uint32_t)op[6];
         const s8v q2 = sload_props(a, psi);
-        if (flags & MTE_F_REWRITE) {
+        if constexpr (K == kPack4) {
+          // the set folded by props_kernel into (keep, val); a rewrite keeps nothing
+          const bool rw = (flags & MTE_F_REWRITE) != 0;
+          const uint32_t keep = rw ? 0u : (uint32_t)q2[4], val = (uint32_t)q2[5];
+          // the side key's value of a marker is in its toff register (put_new_v)
+          if (rw && a.side_key < 4u) {
 #pragma unroll
-          for (int kk = 0; kk < kRegPlanes<K>; kk++)
-#pragma unroll
-            for (int j = 0; j < E; j++) R.pr[kk][j] = in[j] ? 0u : R.pr[kk][j];
-          if constexpr (K == kPack4) {
-            // the side key's value of a marker is in its toff register (put_new_v)
-            if (a.side_key < 4u) {
-#pragma unroll
-              for (int j = 0; j < E; j++) {
-                const uint32_t cleared = vpin((R.meta[j] >> 8) ? 0u : R.toff[j]);
-                R.toff[j] = in[j] ? cleared : R.toff[j];
-              }
+            for (int j = 0; j < E; j++) {
+              const uint32_t cleared = vpin((R.meta[j] >> 8) ? 0u : R.toff[j]);
+              R.toff[j] = in[j] ? cleared : R.toff[j];
             }
           }
+#pragma unroll
+          for (int j = 0; j < E; j++) R.pr[0][j] = in[j] ? ((R.pr[0][j] & keep) | val) : R.pr[0][j];
+        } else {
+          if (flags & MTE_F_REWRITE) {
+#pragma unroll
+            for (int kk = 0; kk < kRegPlanes<K>; kk++)
+#pragma unroll
+              for (int j = 0; j < E; j++) R.pr[kk][j] = in[j] ? 0u : R.pr[kk][j];
+          }
+          apply_props<E, K>(R.pr, in, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
         }
-        apply_props<E, K>(R.pr, in, (uint32_t)q2[0], (uint32_t)q2[1], (uint32_t)q2[2], psi, a);
         MTE_STAT(st[kStPwrites] += cnt * (uint32_t)q2[3];)
       }
     }
   }
   return 0;
+}
+
+// zamboni of a pass-1 tier after minSeq rose to msn: drop the tombstones with
+// removedSeq <= msn (padding included), set D.n.  Returns true when the
+// document now fits a smaller register tier (the burst ends).
+template <int E, int K>
+__device__ __forceinline__ bool zamboni_v(Regs<E, K>& R, DocRun& D, int n, int32_t msn, uint32_t* zlds, int emin) {
+  if constexpr (E == 1) {
+    // each kept slot pushes its fields to its compacted lane (ds_permute)
+    const bool keep = R.rseq[0] > msn;
+    const uint64_t mk = __ballot(keep);
+    const int n_new = __popcll(mk);
+    if (n_new != n) {
+      const int addr = (keep ? (int)lanes_below(mk) : kWave - 1) << 2;
+      R.len[0] = __builtin_amdgcn_ds_permute(addr, R.len[0]);
+      R.seq[0] = __builtin_amdgcn_ds_permute(addr, R.seq[0]);
+      R.rseq[0] = __builtin_amdgcn_ds_permute(addr, R.rseq[0]);
+      R.rmask[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.rmask[0]);
+      R.meta[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.meta[0]);
+      R.toff[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.toff[0]);
+#pragma unroll
+      for (int kk = 0; kk < kRegPlanes<K>; kk++)
+        R.pr[kk][0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.pr[kk][0]);
+      const bool pad = lane_id() >= n_new;
+      R.rseq[0] = pad ? kPad : R.rseq[0];
+      R.len[0] = pad ? 0 : R.len[0];
+      D.n = n_new;
+    }
+  } else {
+    const int n_new = zamboni_lds<E, K>(R, n, msn, zlds);
+    if (n_new != n) {
+      D.n = n_new;
+      // drop to a smaller register tier once the doc fits in half of it
+      if (E > emin && n_new + 2 + 16 <= 32 * E) return true;
+    }
+  }
+  return false;
 }
 
 template <int E, int K, bool S>
@@ -479,36 +523,150 @@ __device__ __forceinline__ int doc_step_v(Regs<E, K>& R, DocRun& D, uint32_t (&s
     D.cur_seq = s;
     if (msn > D.min_seq) {
       D.min_seq = msn;
-      // zamboni: drop tombstones with removedSeq <= minSeq (padding included)
-      if constexpr (E == 1) {
-        // each kept slot pushes its fields to its compacted lane (ds_permute)
-        const bool keep = R.rseq[0] > msn;
-        const uint64_t mk = __ballot(keep);
-        const int n_new = __popcll(mk);
-        if (n_new != n) {
-          const int addr = (keep ? (int)lanes_below(mk) : kWave - 1) << 2;
-          R.len[0] = __builtin_amdgcn_ds_permute(addr, R.len[0]);
-          R.seq[0] = __builtin_amdgcn_ds_permute(addr, R.seq[0]);
-          R.rseq[0] = __builtin_amdgcn_ds_permute(addr, R.rseq[0]);
-          R.rmask[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.rmask[0]);
-          R.meta[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.meta[0]);
-          R.toff[0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.toff[0]);
+      if (zamboni_v<E, K>(R, D, n, msn, zlds, emin)) return 1;
+    }
+  }
+  return 0;
+}
+
+// ---- block decode ------------------------------------------------------------
+// The tiers E <= kBlockEmax take their records 64 at a time: lane i holds
+// record D.k + i whole, and what depends on the records alone -- the field
+// decode, the client / type checks and the whole collab window, a prefix
+// computation over the records -- is done once per block with vector
+// instructions.  The op loop then reads a record's words with v_readlane at a
+// scalar lane index (no load, no wait per op) and its window work is one bit
+// test.  E = 4 keeps doc_step_v's per-op fetch: it has no registers to spare.
+constexpr int kBlockEmax = 2;
+
+template <int CTRL, int ROWMASK = 0xf>
+__device__ __forceinline__ int32_t dpp_or(int32_t old, int32_t v) {
+  // disabled / out-of-range source lanes produce `old`
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWMASK, 0xf, false);
+}
+
+// inclusive running maximum over the 64 lanes (wave_incl_scan's shape); lo =
+// INT32_MIN, the identity of max, in a register of the caller's
+__device__ __forceinline__ int32_t wave_incl_max(int32_t v, int32_t lo) {
+  int32_t t;
+  t = dpp_or<kRowShr1>(lo, v), v = v > t ? v : t;
+  t = dpp_or<kRowShr2>(lo, v), v = v > t ? v : t;
+  t = dpp_or<kRowShr4>(lo, v), v = v > t ? v : t;
+  t = dpp_or<kRowShr8>(lo, v), v = v > t ? v : t;
+  t = dpp_or<kRowBcast15, 0xa>(lo, v), v = v > t ? v : t;
+  t = dpp_or<kRowBcast31, 0xc>(lo, v), v = v > t ? v : t;
+  return v;
+}
+
+// Up to kend - D.k records of one document, block by block.  Returns like
+// doc_step_v: 0 (all applied), 1 (re-pick the tier) or a negative MTE_E_*; D is
+// then exactly what doc_step_v leaves record after record, so the next burst
+// decodes afresh from D.k.
+template <int E, int K, bool S>
+__device__ __forceinline__ int block_run(Regs<E, K>& R, DocRun& D, uint32_t (&st)[kNumStats], const ReplayArgs& a,
+                                         uint32_t* zlds, int emin, uint32_t kend) {
+  const int lim = kWave * E < (int)a.cap ? kWave * E : (int)a.cap;
+  while (D.k < kend) {
+    const uint32_t nb = kend - D.k < (uint32_t)kWave ? kend - D.k : (uint32_t)kWave;
+    // ---- the block: record D.k + lane, zero past its end ----------------------
+    // the lane index and the scans' identity are made here, per block, behind
+    // an asm: as loop invariants they are hoisted out of the kernel's burst
+    // loop and then live (and spill) across the E = 4 tier's code
+    uint32_t lane = (uint32_t)lane_id();
+    int32_t lo32 = INT32_MIN;
+    asm volatile("" : "+v"(lane), "+v"(lo32));
+    const bool valid = lane < nb;
+    const uint4* rp = D.recp + 2 * (D.k + (valid ? lane : 0u));
+    const uint4 lo = rp[0], hi = rp[1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
-          for (int kk = 0; kk < kRegPlanes<K>; kk++)
-            R.pr[kk][0] = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int32_t)R.pr[kk][0]);
-          const bool pad = lane_id() >= n_new;
-          R.rseq[0] = pad ? kPad : R.rseq[0];
-          R.len[0] = pad ? 0 : R.len[0];
-          D.n = n_new;
-        }
-      } else {
-        const int n_new = zamboni_lds<E, K>(R, n, msn, zlds);
-        if (n_new != n) {
-          D.n = n_new;
-          // drop to a smaller register tier once the doc fits in half of it
-          if (E > emin && n_new + 2 + 16 <= 32 * E) return 1;
+    for (int i = 0; i < 8; i++) w[i] = valid ? w[i] : 0u;
+    const uint32_t vtype = w[3] & 0xffu, vc = (w[3] >> 8) & 0xffu;
+    const bool vlive = vtype != MTE_OP_NOOP, vend = ((w[3] >> 16) & MTE_F_MSG_END) != 0;
+    const int32_t vs = (int32_t)w[0], vmsn = (int32_t)w[2];
+    // the window before each record: on the valid prefix the running maximum of
+    // the ENDs' seq is "the last END's seq" and that of their min_seq is minSeq
+    // (a lower value there is itself an error); behind the first bad record
+    // nothing is read
+    const int32_t cur_raw = wave_incl_max(vend ? vs : lo32, lo32);
+    const int32_t min_raw = wave_incl_max(vend ? vmsn : lo32, lo32);
+    int32_t cur_b = dpp_or<kWaveShr1>(lo32, cur_raw), min_b = dpp_or<kWaveShr1>(lo32, min_raw);
+    cur_b = cur_b > D.cur_seq ? cur_b : D.cur_seq;
+    min_b = min_b > D.min_seq ? min_b : D.min_seq;
+    const int32_t cur_after = cur_raw > D.cur_seq ? cur_raw : D.cur_seq;  // lane i: cur_seq after record i
+    const bool bad_pre = vc >= MTE_MAX_CLIENTS || (vtype > MTE_OP_ANNOTATE && vtype != MTE_OP_NOOP);
+    const bool bad_win = (vlive & (vs <= cur_b)) | (vend & (vs < cur_b)) | ((vlive | vend) & (vmsn < min_b)) |
+                         (vend & (vmsn > vs));
+    const uint64_t mpre = __ballot(valid && bad_pre), mbad = mpre | __ballot(valid && bad_win);
+    const uint32_t stop = mbad ? (uint32_t)__builtin_ctzll(mbad) : nb;  // the first bad record
+    const bool stop_pre = mbad && ((mpre >> stop) & 1ull);
+    // where the window advances and the zamboni runs (below the stop record)
+    const uint64_t zam = __ballot(valid && vend && vmsn > min_b) & (stop < 64u ? (1ull << stop) - 1ull : ~0ull);
+    // a record that only violates the window is applied before its error shows
+    const uint32_t nrun = stop + ((mbad && !stop_pre) ? 1u : 0u);
+
+    uint32_t i = 0;
+    int rc = 0;
+    for (; i < nrun; i++) {
+      if (D.n + 2 > lim) {
+        rc = 1;
+        break;
+      }
+      if constexpr (S) {
+        if (st[kStOps] >= (1u << 20)) {
+          rc = 1;
+          break;
         }
       }
+      s8v op;
+#pragma unroll
+      for (int j = 0; j < 8; j++) op[j] = (int32_t)rdlane(w[j], (int)i);
+      const uint32_t w3 = (uint32_t)op[3];
+      const uint32_t type = w3 & 0xffu, c = (w3 >> 8) & 0xffu, flags = w3 >> 16;
+      MTE_STAT(st[kStOps]++;)
+      MTE_STAT(st[kStMaxSegs] = (uint32_t)D.n > st[kStMaxSegs] ? (uint32_t)D.n : st[kStMaxSegs];)
+      int n = D.n;
+      if (type <= MTE_OP_ANNOTATE) {
+        MTE_STAT(st[kStScanned] += (uint32_t)n;)
+        int32_t tot, dlen;
+        rc = seg_op_v<E, K, S, false>(R, n, op, type, c, flags, D.min_seq, (D.flags & MTE_DOC_NEW_LENGTH_CALC) != 0, 0,
+                                      true, tot, dlen, a, st);
+        if (rc) break;
+      }
+      D.n = n;
+      D.k++;
+      if ((zam >> i) & 1ull) {
+        const int32_t msn = op[2];
+        D.min_seq = msn;
+        if (zamboni_v<E, K>(R, D, n, msn, zlds, emin)) {
+          i++;
+          rc = 1;
+          break;
+        }
+      }
+    }
+    // i records of the block are applied: cur_seq is the last END's seq among
+    // them.  A stop record that was applied is not counted: window_error sets
+    // cur_seq itself where the reference does
+    const bool stopped = rc == 0 && mbad;  // the loop reached the stop record
+    const uint32_t done = (stopped && !stop_pre) ? stop : i;
+    if (done) D.cur_seq = rdlane(cur_after, (int)done - 1);
+    if (rc) return rc;
+    if (stopped) {
+      const uint32_t w3 = rdlane(w[3], (int)stop);
+      const uint32_t type = w3 & 0xffu, c = (w3 >> 8) & 0xffu, flags = w3 >> 16;
+      if (stop_pre) {  // nothing of the record is applied
+        if (D.n + 2 > lim) return 1;
+        if constexpr (S) {
+          if (st[kStOps] >= (1u << 20)) return 1;
+        }
+        if (c >= MTE_MAX_CLIENTS) return MTE_E_CLIENT_RANGE;
+        MTE_STAT(st[kStOps]++;)
+        MTE_STAT(st[kStMaxSegs] = (uint32_t)D.n > st[kStMaxSegs] ? (uint32_t)D.n : st[kStMaxSegs];)
+        return MTE_E_INVALID_ARG;
+      }
+      return window_error(D, type != MTE_OP_NOOP, (flags & MTE_F_MSG_END) != 0, (int32_t)rdlane(w[0], (int)stop),
+                          (int32_t)rdlane(w[2], (int)stop));
     }
   }
   return 0;
