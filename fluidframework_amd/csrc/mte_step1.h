@@ -17,7 +17,11 @@
 // decodes it, checks client and type and runs the whole collab window as a
 // prefix computation (running maxima of the ENDs' seq and min_seq), and the op
 // loop reads a record with v_readlane at a scalar lane index and tests one bit
-// for "minSeq advances here".  E = 4 keeps the per-op fetch and window of
+// for "minSeq advances here"; the words only some ops use (minSeq, the text
+// offset, the property sets) are read where they are used (LaneWords).  The
+// shift itself goes through the LDS crossbar at E = 1 (one ds_bpermute per
+// plane) and at E = 2 (two, and two selects), plane by plane through DPP at
+// E = 4 (shift_v).  E = 4 keeps the per-op fetch and window of
 // doc_step_v.  On the kPack4 layout a property set is applied as the (keep,
 // val) pair props_kernel folded it into (mte_kernels.h), whatever its size.
 #pragma once
@@ -92,9 +96,7 @@ __device__ __forceinline__ void perm_plane(T (&F)[E], int addr) {
   F[0] = perm1(F[0], addr);
 }
 
-constexpr int kShiftSeqEmin = 4;  // tiers with E >= this shift one plane at a time (register-light)
-
-// one plane of shift_v: its two cross-lane moves, then its selects.  The E = 4
+// one plane of shift_v at E = 4: its two cross-lane moves, then its selects.  The E = 4
 // tier shifts plane by plane: moving all 13 planes' neighbours first needs 52
 // temporaries on top of 40 state registers, which spilled the whole pass-1
 // kernel (its register budget is that of its largest tier)
@@ -110,20 +112,55 @@ __device__ __forceinline__ void shift_plane(T (&F)[E], const bool (&g1)[E], cons
   }
 }
 
+// one plane of shift_v at E = 2: slot 0 pulled through a0, slot 1 through a1
+// (byte addresses of the source lanes), then one select per slot: slot 0 takes
+// the slot-1 pull where it moves by one (once0), slot 1 its own lane's old
+// slot 0 where it moves by one (once1)
+template <typename T>
+__device__ __forceinline__ void pull_plane2(T (&F)[2], int a0, int a1, bool once0, bool once1) {
+  const T b0 = perm1(F[0], a0), b1 = perm1(F[1], a1);
+  F[1] = once1 ? F[0] : b1;
+  F[0] = once0 ? b1 : b0;
+}
+
 // new[i] = old[i - d(i)], d = g1 + g2 (g2 implies g1; flag words), for every
 // plane and the NX extra per-slot values X.  E == 1: lane l pulls lane l - d(l)
 // through the LDS crossbar (ds_bpermute: one LDS-pipe instruction per plane
-// instead of two DPP moves and two selects on the VALU).  E > 1: the two
-// cross-lane moves of every plane first (DPP), then the selects.
+// instead of two DPP moves and two selects on the VALU).  E == 2: two pulls and
+// two selects per plane (below).  E == 4: two DPP moves and the selects, plane
+// by plane (shift_plane).
 template <int E, int K, int NX>
 __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX : 1][E], uint32_t g1w,
                                         uint32_t g2w) {
-  bool g1[E], g2[E];
-  if constexpr (E > 1) {
-    funpack<E>(g1w, g1);
-    funpack<E>(g2w, g2);
-  }
-  if constexpr (E == 1) {
+  if constexpr (E == 2) {
+    // Slot j of lane l is global index 2l + j, and d is non-decreasing in i and
+    // never jumps by two, so a lane's (d0, d1) is one of (0,0), (0,1), (1,1),
+    // (1,2), (2,2).  Slot 0 wants lane l's slot 0 (d0 = 0), lane l-1's slot 1
+    // (d0 = 1) or lane l-1's slot 0 (d0 = 2); slot 1 wants lane l's slot 1
+    // (d1 = 0), lane l's slot 0 (d1 = 1) or lane l-1's slot 1 (d1 = 2).  So the
+    // slot-0 plane is pulled from lane l - (d0 == 2) and the slot-1 plane from
+    // lane l - (d0 >= 1): at (1,2) both slots want that one value, at (1,1)
+    // slot 1 takes its own lane's slot 0 and the pull serves slot 0 alone, and
+    // d1 = 2 implies d0 >= 1.  The crossbar wraps modulo 64, so lane 0 must not
+    // pull from lane -1 into a slot that is kept: its slot 1 (i = 1) never moves
+    // by two, and its slot 0 moves only for an insert before the first segment,
+    // which then overwrites the slot whole (put_new_v).
+    const uint32_t once = vpin(g1w & ~g2w);  // bit j: d_j == 1
+    const int self = lane_id() << 2;
+    const int a0 = self - (int)((g2w & 1u) << 2), a1 = self - (int)((g1w & 1u) << 2);
+    const bool o0 = fget(once, 0), o1 = fget(once, 1);
+    // what the caller's piece arithmetic reads first goes first
+#pragma unroll
+    for (int x = 0; x < NX; x++) pull_plane2(X[x], a0, a1, o0, o1);
+    pull_plane2(R.len, a0, a1, o0, o1);
+    pull_plane2(R.toff, a0, a1, o0, o1);
+    pull_plane2(R.seq, a0, a1, o0, o1);
+    pull_plane2(R.rseq, a0, a1, o0, o1);
+    pull_plane2(R.rmask, a0, a1, o0, o1);
+    pull_plane2(R.meta, a0, a1, o0, o1);
+#pragma unroll
+    for (int k = 0; k < kRegPlanes<K>; k++) pull_plane2(R.pr[k], a0, a1, o0, o1);
+  } else if constexpr (E == 1) {
     const int addr = (lane_id() - (int)g1w - (int)g2w) << 2;
     perm_plane<E>(R.len, addr);
     perm_plane<E>(R.seq, addr);
@@ -135,7 +172,10 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
     for (int k = 0; k < kRegPlanes<K>; k++) perm_plane<E>(R.pr[k], addr);
 #pragma unroll
     for (int x = 0; x < NX; x++) perm_plane<E>(X[x], addr);
-  } else if constexpr (E >= kShiftSeqEmin) {
+  } else {
+    bool g1[E], g2[E];
+    funpack<E>(g1w, g1);
+    funpack<E>(g2w, g2);
     shift_plane<E>(R.len, g1, g2);
     shift_plane<E>(R.seq, g1, g2);
     shift_plane<E>(R.rseq, g1, g2);
@@ -146,48 +186,20 @@ __device__ __forceinline__ void shift_v(Regs<E, K>& R, int32_t (&X)[NX > 0 ? NX 
     for (int k = 0; k < kRegPlanes<K>; k++) shift_plane<E>(R.pr[k], g1, g2);
 #pragma unroll
     for (int x = 0; x < NX; x++) shift_plane<E>(X[x], g1, g2);
-  } else {
-    constexpr int NF = kFieldPlanes + kRegPlanes<K> + NX;
-    uint32_t last[NF], last2[NF];
-    shift_grab<E, NF>(last, last2, 0, R.len);
-    shift_grab<E, NF>(last, last2, 1, R.seq);
-    shift_grab<E, NF>(last, last2, 2, R.rseq);
-    shift_grab<E, NF>(last, last2, 3, R.rmask);
-    shift_grab<E, NF>(last, last2, 4, R.meta);
-    shift_grab<E, NF>(last, last2, 5, R.toff);
-#pragma unroll
-    for (int k = 0; k < kRegPlanes<K>; k++) shift_grab<E, NF>(last, last2, kFieldPlanes + k, R.pr[k]);
-#pragma unroll
-    for (int x = 0; x < NX; x++) shift_grab<E, NF>(last, last2, kFieldPlanes + kRegPlanes<K> + x, X[x]);
-    uint32_t p1[NF], p2[NF];
-#pragma unroll
-    for (int f = 0; f < NF; f++) p1[f] = (uint32_t)lane_prev((int32_t)last[f]);
-#pragma unroll
-    for (int f = 0; f < NF; f++) p2[f] = (uint32_t)lane_prev((int32_t)last2[f]);
-    shift_apply<E, NF>(R.len, p1, p2, 0, g1, g2);
-    shift_apply<E, NF>(R.seq, p1, p2, 1, g1, g2);
-    shift_apply<E, NF>(R.rseq, p1, p2, 2, g1, g2);
-    shift_apply<E, NF>(R.rmask, p1, p2, 3, g1, g2);
-    shift_apply<E, NF>(R.meta, p1, p2, 4, g1, g2);
-    shift_apply<E, NF>(R.toff, p1, p2, 5, g1, g2);
-#pragma unroll
-    for (int k = 0; k < kRegPlanes<K>; k++) shift_apply<E, NF>(R.pr[k], p1, p2, kFieldPlanes + k, g1, g2);
-#pragma unroll
-    for (int x = 0; x < NX; x++) shift_apply<E, NF>(X[x], p1, p2, kFieldPlanes + kRegPlanes<K> + x, g1, g2);
   }
 }
 
 // the inserted segment at the slots flagged in `atw` (mergeTree.ts:1599-1611,
 // textSegment.ts:40-48, mergeTreeNodes.ts:602-609)
-template <int E, int K, bool S>
-__device__ __forceinline__ void put_new_v(Regs<E, K>& R, uint32_t atw, const s8v& op, uint32_t c,
+template <int E, int K, bool S, typename LW>
+__device__ __forceinline__ void put_new_v(Regs<E, K>& R, uint32_t atw, const s8v& op, const LW& late, uint32_t c,
                                           uint32_t flags, const ReplayArgs& a, uint32_t (&st)[kNumStats]) {
   const int32_t s = op[0], pos2 = op[5];
   const bool marker = (flags & MTE_F_MARKER) != 0;
   const int32_t nlen = marker ? 1 : pos2;
   const uint32_t meta = (c + 1u) | (marker ? (1u + (uint32_t)pos2) << 8 : 0u);
-  uint32_t toff = marker ? 0u : a.text_base + (uint32_t)op[6];
-  const uint32_t psi = (uint32_t)op[7];
+  uint32_t toff = marker ? 0u : a.text_base + (uint32_t)late.w6();
+  const uint32_t psi = (uint32_t)late.w7();
   uint32_t pr[kRP<K>][1];
   const bool one[1] = {true};
 #pragma unroll
@@ -230,9 +242,14 @@ constexpr int kNextChunk = 2;
 // op's positions are taken relative to `off`, the chunk's first position in
 // the op's perspective; *tot is the chunk's length in that perspective before
 // the op and *dlen its change (+ inserted units, - units the remover saw).
-template <int E, int K, bool S, bool CH>
-__device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, uint32_t type, uint32_t c,
-                                        uint32_t flags, int32_t m, bool newcalc, int32_t off, bool last,
+//
+// Words 6 and 7 of the record come through `late` (w6(), w7()): only an insert
+// reads word 7 (its property set) and only a text insert or an annotate that
+// marks something reads word 6, so a caller that holds the records in lanes
+// (block_run) reads them there and not for every op.
+template <int E, int K, bool S, bool CH, typename LW>
+__device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, const LW& late, uint32_t type,
+                                        uint32_t c, uint32_t flags, int32_t m, bool newcalc, int32_t off, bool last,
                                         int32_t& tot, int32_t& dlen, const ReplayArgs& a,
                                         uint32_t (&st)[kNumStats]) {
   const int base = lane_id() * E;
@@ -306,7 +323,7 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
       MTE_STAT(st[kStWritten] += 1;)
     }
     at = vpin(at);
-    if (nlen > 0) put_new_v<E, K, S>(R, at, op, c, flags, a, st);
+    if (nlen > 0) put_new_v<E, K, S>(R, at, op, late, c, flags, a, st);
     if constexpr (CH) dlen = nlen > 0 ? nlen : 0;
   } else {
     // markRangeRemoved / annotateRange: ensureIntervalBoundary at both ends
@@ -407,7 +424,7 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
         }
       } else if (cnt > 0) {
         // PropertiesManager.addProperties (segmentPropertiesManager.ts:63-151)
-        const uint32_t psi = (uint32_t)op[6];
+        const uint32_t psi = (uint32_t)late.w6();
         const s8v q2 = sload_props(a, psi);
         if constexpr (K == kPack4) {
           // the set folded by props_kernel into (keep, val); a rewrite keeps nothing
@@ -437,6 +454,21 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, ui
     }
   }
   return 0;
+}
+
+// words 6 and 7 of a record that is already in scalars
+struct OpWords {
+  const s8v& op;
+  __device__ __forceinline__ int32_t w6() const { return op[6]; }
+  __device__ __forceinline__ int32_t w7() const { return op[7]; }
+};
+
+template <int E, int K, bool S, bool CH>
+__device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, uint32_t type, uint32_t c,
+                                        uint32_t flags, int32_t m, bool newcalc, int32_t off, bool last,
+                                        int32_t& tot, int32_t& dlen, const ReplayArgs& a,
+                                        uint32_t (&st)[kNumStats]) {
+  return seg_op_v<E, K, S, CH>(R, n, op, OpWords{op}, type, c, flags, m, newcalc, off, last, tot, dlen, a, st);
 }
 
 // zamboni of a pass-1 tier after minSeq rose to msn: drop the tombstones with
@@ -545,6 +577,24 @@ __device__ __forceinline__ int32_t dpp_or(int32_t old, int32_t v) {
   return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWMASK, 0xf, false);
 }
 
+// Record i's words 2, 6 and 7 out of the block's lanes, read where an op needs
+// them.  A v_readlane has no side effect, so the compiler would hoist it to
+// the top of the op loop beside the other words, one VALU instruction per word
+// and op; the lane index passes through a volatile asm at each use, which
+// stays under the branch it is written in.
+struct LaneWords {
+  uint32_t v2, v6, v7;  // the words of record D.k + lane
+  uint32_t i;           // the record's lane, wave-uniform
+  __device__ __forceinline__ int32_t at(uint32_t v) const {
+    uint32_t l = i;
+    asm volatile("" : "+s"(l));
+    return (int32_t)rdlane(v, (int)l);
+  }
+  __device__ __forceinline__ int32_t w2() const { return at(v2); }
+  __device__ __forceinline__ int32_t w6() const { return at(v6); }
+  __device__ __forceinline__ int32_t w7() const { return at(v7); }
+};
+
 // inclusive running maximum over the 64 lanes (wave_incl_scan's shape); lo =
 // INT32_MIN, the identity of max, in a register of the caller's
 __device__ __forceinline__ int32_t wave_incl_max(int32_t v, int32_t lo) {
@@ -618,9 +668,13 @@ __device__ __forceinline__ int block_run(Regs<E, K>& R, DocRun& D, uint32_t (&st
           break;
         }
       }
-      s8v op;
+      // words 0, 1, 3, 4, 5 of record i for every op; 2 (minSeq), 6 and 7 where
+      // they are used (LaneWords)
+      s8v op = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int j = 0; j < 8; j++) op[j] = (int32_t)rdlane(w[j], (int)i);
+      for (int j = 0; j < 6; j++)
+        if (j != 2) op[j] = (int32_t)rdlane(w[j], (int)i);
+      const LaneWords late{w[2], w[6], w[7], i};
       const uint32_t w3 = (uint32_t)op[3];
       const uint32_t type = w3 & 0xffu, c = (w3 >> 8) & 0xffu, flags = w3 >> 16;
       MTE_STAT(st[kStOps]++;)
@@ -629,14 +683,14 @@ __device__ __forceinline__ int block_run(Regs<E, K>& R, DocRun& D, uint32_t (&st
       if (type <= MTE_OP_ANNOTATE) {
         MTE_STAT(st[kStScanned] += (uint32_t)n;)
         int32_t tot, dlen;
-        rc = seg_op_v<E, K, S, false>(R, n, op, type, c, flags, D.min_seq, (D.flags & MTE_DOC_NEW_LENGTH_CALC) != 0, 0,
-                                      true, tot, dlen, a, st);
+        rc = seg_op_v<E, K, S, false>(R, n, op, late, type, c, flags, D.min_seq,
+                                      (D.flags & MTE_DOC_NEW_LENGTH_CALC) != 0, 0, true, tot, dlen, a, st);
         if (rc) break;
       }
       D.n = n;
       D.k++;
       if ((zam >> i) & 1ull) {
-        const int32_t msn = op[2];
+        const int32_t msn = late.w2();
         D.min_seq = msn;
         if (zamboni_v<E, K>(R, D, n, msn, zlds, emin)) {
           i++;
