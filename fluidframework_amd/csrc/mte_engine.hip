@@ -105,9 +105,12 @@ __global__ void rel_route_kernel(DocHdr* hdr, const uint32_t* docs, uint32_t n, 
   DocHdr* h = hdr + docs[i];
   if (h->status != 0) return;
   const uint32_t f = h->flags;
-  if (f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) return;
-  if (!(f & (MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_ROUND_SYNC))) {
-    if (!(f & MTE_DOC_EVENTS)) h->flags = f | kHdrTreeHbmFlag;
+  // (the tests this replaces sent MTE_DOC_ROUND_SYNC | MTE_DOC_EVENTS on to the
+  // flat branch; mte_load_docs refuses that combination)
+  const DocOwner own = doc_owner(f);
+  if (own == kOwnHtree) return;
+  if (own == kOwnTree) {
+    h->flags = f | kHdrTreeHbmFlag;
     return;
   }
   if (chunked) h->status = MTE_E_UNSUPPORTED;
@@ -123,6 +126,9 @@ __global__ void rel_route_kernel(DocHdr* hdr, const uint32_t* docs, uint32_t n, 
 // reloadFromSegments' blocks of 7 (image_kernel writes the tree words).
 // device copy of mte_doc_init::flags: the load text holds a '\n' (engine-internal)
 constexpr uint32_t kInitNl = 0x80000000u;
+// the MTE_DOC_* bits: what a header and DocState::flags keep of mte_doc_init::flags
+constexpr uint32_t kDocFlags = MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_ROUND_SYNC | MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS |
+                               MTE_DOC_REFS | MTE_DOC_SLIDE_EVENTS | MTE_DOC_MAINT_EVENTS | MTE_DOC_TREE;
 
 __global__ void reset_kernel(DocHdr* hdr, SegSoA soa, uint32_t cap, const mte_doc_init* inits,
                              const uint32_t* init_props, uint32_t n_keys, uint32_t n_docs,
@@ -131,19 +137,22 @@ __global__ void reset_kernel(DocHdr* hdr, SegSoA soa, uint32_t cap, const mte_do
   if (d >= n_docs) return;
   const mte_doc_init in = inits[d];
   const uint32_t n_img = img_off ? (uint32_t)(img_off[d + 1] - img_off[d]) : 0u;
-  const bool flat_legacy = (in.flags & (MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_ROUND_SYNC)) == MTE_DOC_ROUND_SYNC;
+  // (the bit tests these two replace answered otherwise only for MTE_DOC_ROUND_SYNC
+  // with MTE_DOC_TREE, a local client or delta events, which mte_load_docs refuses)
+  const bool flat_legacy = doc_owner(in.flags) == kOwnFlatRs;
   // documents with the reference's tree: legacy ones (register tiers, then the
   // HBM tree pass) and the HBM tree pass's own (a local client, or legacy with
   // delta events)
-  const bool legacy = tree != nullptr && (!(in.flags & (MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_ROUND_SYNC)) ||
-                                          (in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)));
+  const bool legacy = tree != nullptr && doc_has_tree(in.flags);
+  // the document's layout, not its route: a legacy document with delta events
+  // is the HBM tree pass's own without the local planes (mte_htree.h kLocalPlanes)
+  const bool lplanes = (in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) != 0;
   DocHdr h;
   h.nseg = n_img ? (int32_t)n_img : (in.text_len > 0 || legacy ? 1 : 0);
   h.min_seq = in.min_seq;
   h.cur_seq = in.cur_seq;
   h.status = 0;
-  h.flags = in.flags & (MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_ROUND_SYNC | MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS | MTE_DOC_REFS |
-                        MTE_DOC_SLIDE_EVENTS | MTE_DOC_MAINT_EVENTS | MTE_DOC_TREE);
+  h.flags = in.flags & kDocFlags;
   h.resume = 0;
   h.pad0 = h.pad1 = 0;
   if (legacy) {
@@ -164,10 +173,10 @@ __global__ void reset_kernel(DocHdr* hdr, SegSoA soa, uint32_t cap, const mte_do
     st[kHsHeapN] = 0u;
     st[kHsLseq] = 0u;
     st[kHsRhi] = 0u;
-    st[kHsEntered] = (in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) ? 1u : 0u;
+    st[kHsEntered] = lplanes ? 1u : 0u;
     st[kHsWin] = 0u;  // no cached local partials
   }
-  if (in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) {  // nothing pending, no removers >= 32 (mte_htree.h planes)
+  if (lplanes) {  // nothing pending, no removers >= 32 (mte_htree.h planes)
     const uint32_t nz = n_img ? n_img : 1u;
     for (uint32_t k = 0; k < 2 * kt + 6; k++)  // the local planes (mte_htree.h kLocalPlanes)
       for (uint32_t x = 0; x < nz; x++) soa.props[(kt + k) * soa.plane_stride + (uint64_t)d * cap + x] = 0u;
@@ -585,11 +594,11 @@ struct BatchSlot {
   }
 };
 
-// the mte_load_segments image (SoA, 6 + kt planes at stride n)
+// the mte_load_segments image (SoA, 6 + kt planes at stride n); replaced by
+// each mte_load_segments (free_image), on its own schedule within a load
 struct SegImage {
-  uint32_t* img = nullptr;
-  uint32_t* doc = nullptr;
-  uint64_t* off = nullptr;
+  DevBuf<uint32_t> img, doc;
+  DevBuf<uint64_t> off;
   uint64_t n = 0;
   ImgConst uc = {};  // the image's uniform planes (image_kernel)
 };
@@ -598,6 +607,9 @@ struct SegImage {
 // survives a reload.
 struct DocState {
   uint32_t n_docs = 0;
+  // every device allocation behind the pointers below (doc_alloc), in the
+  // order made: all free_docs has to know
+  std::vector<void*> owned;
   bool rounds_carried = false;  // a round-phase run laid documents out in the arena since the load / reset
   DocHdr* hdr = nullptr;
   SegSoA soa{};
@@ -616,7 +628,6 @@ struct DocState {
   RoundArgs rd{};
   // tile-parallel digest of big-document contexts (dg_*_kernel), allocated at
   // the first digest of such a context
-  void* d_dgt = nullptr;
   DigestTiles dgt{};
   uint32_t* d_pairs = nullptr;  // pass-1 doc pairs (new length calc documents)
   uint32_t n_pairs = 0;         // pass-1 waves
@@ -635,16 +646,14 @@ struct DocState {
   uint32_t* d_htree_docs = nullptr; // the candidates
   uint32_t n_htree = 0;
   std::vector<uint32_t> h_htree_docs;
-  std::vector<uint8_t> h_legacy;    // per doc: it carries tree words
-  std::vector<uint8_t> h_local;     // per doc: 1 MTE_DOC_LOCAL_CLIENT, 2 MTE_DOC_TREE (the HBM tree pass's)
-  std::vector<uint8_t> h_events;    // per doc: MTE_DOC_EVENTS
+  // per doc (always n_docs long): its MTE_DOC_* flags as mte_load_docs accepted
+  // them; doc_owner / doc_has_tree (mte_kernels.h) say which pass replays it
+  std::vector<uint32_t> flags;
   // the flat HBM-streamed pass's own documents (new length calc with delta
   // events, no local client): BatchSlot::sorder
   std::vector<uint32_t> h_sdocs;
   // local references of the MTE_DOC_REFS documents (mte_stream.h): ref_cap slots
   // per document, zeroed at every reset
-  std::vector<uint8_t> h_refs;      // per doc: MTE_DOC_REFS
-  std::vector<uint8_t> h_slides;    // per doc: MTE_DOC_SLIDE_EVENTS (with REFS and EVENTS)
   std::vector<uint32_t> h_ref_hi;   // per doc: reference slots its MTE_OP_REF records used so far (+1)
   uint2* d_refs = nullptr;
   bool any_maint = false;           // a document records maintenance (the HBM tree pass's M build)
@@ -755,10 +764,11 @@ int join_tail(mte_ctx* c) {
   c->tail_rc = 0;
   return rc;
 }
-#define JOIN_TAIL(c)                              \
-  do {                                            \
-    if (const int jr_ = join_tail(c)) return jr_; \
+#define MTECHK(expr)                        \
+  do {                                      \
+    if (const int rc_ = (expr)) return rc_; \
   } while (0)
+#define JOIN_TAIL(c) MTECHK(join_tail(c))
 
 // drop this context's reference to its communicator; the last one destroys it
 ncclResult_t comm_release(mte_ctx* c) {
@@ -809,9 +819,7 @@ int grow(mte_ctx* c, DevBuf<T>& b, uint64_t need, bool keep = false, uint64_t ke
 
 void free_image(mte_ctx* c) {
   SegImage& im = c->docs.image;
-  void* ps[] = {im.img, im.doc, im.off};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
+  free_buf(im.img), free_buf(im.doc), free_buf(im.off);
   im = SegImage{};
 }
 
@@ -819,15 +827,31 @@ void free_image(mte_ctx* c) {
 // buffers; their order of the HBM tree pass's documents is of this load.
 void free_docs(mte_ctx* c) {
   free_image(c);
-  DocState& d = c->docs;
-  void* ps[] = {d.hdr, d.soa.len, d.stats, d.d_inits, d.d_init_props, d.d_digest, d.d_wclock, d.d_dgt, d.d_pairs,
-                d.d_tree, d.d_heap, d.d_tree_docs, d.d_hheap, d.d_hst, d.d_hscr, d.d_htree_docs, d.d_refs, d.d_rs_docs,
-                d.ch.arena, d.ch.cnt, d.ch.kc, d.ch.sum, d.rd.plan, d.rd.acct, d.rd.rcnt, d.rd.rbuf, d.rd.rflag,
-                d.rd.nch, d.rd.nnew, d.rd.count, d.rd.rchain, d.rd.live, d.rd.gfl, d.rd.rrec};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  d = DocState{};
+  for (void* p : c->docs.owned) (void)hipFree(p);
+  c->docs = DocState{};
   for (BatchSlot& s : c->slot) s.hord_ok = false;
+}
+
+// Device memory of the loaded documents: n elements (at least one, so an empty
+// load still has every buffer) into *p, owned by DocState::owned until
+// free_docs; `zero` clears it on the engine stream.
+template <typename T>
+int doc_alloc(mte_ctx* c, T** p, uint64_t n, bool zero = false) {
+  const uint64_t bytes = (n ? n : 1) * sizeof(T);
+  void* q = nullptr;
+  HIPCHK(c, hipMalloc(&q, bytes));
+  c->docs.owned.push_back(q);
+  *p = static_cast<T*>(q);
+  if (zero) HIPCHK(c, hipMemsetAsync(q, 0, bytes, c->stream));
+  return MTE_OK;
+}
+
+// ... holding a host list
+template <typename T>
+int doc_upload(mte_ctx* c, T** p, const std::vector<T>& v) {
+  MTECHK(doc_alloc(c, p, v.size()));
+  if (!v.empty()) HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return MTE_OK;
 }
 
 int launch_reset(mte_ctx* c) {
@@ -835,15 +859,15 @@ int launch_reset(mte_ctx* c) {
   if (!d.n_docs) return MTE_OK;
   const uint32_t blocks = (d.n_docs + 255) / 256;
   hipLaunchKernelGGL(reset_kernel, dim3(blocks), dim3(256), 0, c->stream, d.hdr, d.soa, c->cap, d.d_inits,
-                     d.d_init_props, c->n_keys, d.n_docs, (const uint64_t*)d.image.off, d.d_tree, c->kt, d.d_hst);
+                     d.d_init_props, c->n_keys, d.n_docs, (const uint64_t*)d.image.off.p, d.d_tree, c->kt, d.d_hst);
   HIPCHK(c, hipGetLastError());
   if (d.d_refs) HIPCHK(c, hipMemsetAsync(d.d_refs, 0, sizeof(uint2) * (size_t)c->ref_cap * d.n_docs, c->stream));
   std::fill(d.h_ref_hi.begin(), d.h_ref_hi.end(), 0u);  // the references are gone
   if (d.image.n) {
     const uint64_t nb = std::min<uint64_t>((d.image.n + 255) / 256, 65536);
     hipLaunchKernelGGL(image_kernel, dim3((uint32_t)nb), dim3(256), 0, c->stream, d.soa, c->cap,
-                       (uint32_t)(kFieldPlanes + c->kt), d.image.img, d.image.n, d.image.doc,
-                       (const uint64_t*)d.image.off, d.image.n, d.d_tree, d.image.uc);
+                       (uint32_t)(kFieldPlanes + c->kt), d.image.img.p, d.image.n, d.image.doc.p,
+                       (const uint64_t*)d.image.off.p, d.image.n, d.d_tree, d.image.uc);
     HIPCHK(c, hipGetLastError());
   }
   c->ran = false;
@@ -996,6 +1020,15 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
   return MTE_OK;  // mte_run joins the tree stream (finish)
 }
 
+// ... of the context's build: property planes kt (0 / 4 / 8), statistics on or off
+int launch_replay_of(mte_ctx* c, const ReplayArgs& a) {
+  using Fn = int (*)(mte_ctx*, const ReplayArgs&);
+  static const Fn of[3][2] = {{launch_replay<0, false>, launch_replay<0, true>},
+                              {launch_replay<4, false>, launch_replay<4, true>},
+                              {launch_replay<8, false>, launch_replay<8, true>}};
+  return of[c->kt / 4][c->stats_on ? 1 : 0](c, a);
+}
+
 // Validation of one op record (the kernels index with these fields, so a bad
 // record must never reach them).  Returns nullptr or the reason.
 const char* bad_op(const mte_op& o, const mte_batch* b, bool local_doc, bool tree_doc, bool refs_doc, uint32_t ref_cap) {
@@ -1100,9 +1133,9 @@ int upload_ops(mte_ctx* c, const mte_batch* b, int w, uint64_t* bad, const char*
         for (uint64_t k = a; k < e; k++) {
           while (d + 1 < b->n_docs && b->op_offsets[d + 1] <= k0 + k) d++;
           const mte_op& o = b->ops[k0 + k];
-          const uint8_t hl = c->docs.h_local.empty() ? 0 : c->docs.h_local[d];
-          const bool refs = !c->docs.h_refs.empty() && c->docs.h_refs[d];
-          const char* r = bad_op(o, b, (hl & 1) != 0, (hl & 2) != 0, refs, c->ref_cap);
+          const uint32_t f = c->docs.flags[d];
+          const bool tree_doc = (f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) == MTE_DOC_TREE;
+          const char* r = bad_op(o, b, (f & MTE_DOC_LOCAL_CLIENT) != 0, tree_doc, (f & MTE_DOC_REFS) != 0, c->ref_cap);
           if (!r && o.type == MTE_OP_RELPOS) {
             const mte_op* nx = k0 + k + 1 < b->op_offsets[d + 1] ? &b->ops[k0 + k + 1] : nullptr;
             if (!nx || nx->type > MTE_OP_ANNOTATE) r = "relative position record not followed by an insert, remove "
@@ -1160,6 +1193,60 @@ int upload_ops(mte_ctx* c, const mte_batch* b, int w, uint64_t* bad, const char*
   std::sort(rd.begin(), rd.end());
   rd.erase(std::unique(rd.begin(), rd.end()), rd.end());
   return MTE_OK;
+}
+
+// ---- one document on the host, for the read-outs ------------------------------
+// the field planes by name (SegSoA's order); the property planes follow at
+// kFieldPlanes, the local planes after those (mte_passes.h local_planes)
+enum Plane { kPlLen = 0, kPlSeq, kPlRseq, kPlRmask, kPlMeta, kPlToff };
+constexpr uint64_t plane_set(int first, int count = 1) { return ((1ull << count) - 1) << first; }
+
+struct DocFetch {
+  DocHdr h{};
+  uint32_t n = 0;             // its segments (nseg, clamped to the capacity)
+  uint64_t mask = 0;          // the planes fetched
+  std::vector<uint32_t> buf;  // words [0, n) of each, in plane order; then the tree words (0 where not fetched)
+  const uint32_t* at(int slot) const { return buf.data() + (size_t)slot * n; }
+  const uint32_t* plane(int p) const { return at(__builtin_popcountll(mask & plane_set(0, p))); }
+  const int32_t* iplane(int p) const { return reinterpret_cast<const int32_t*>(plane(p)); }
+  const uint32_t* tree() const { return at(__builtin_popcountll(mask)); }
+};
+
+// The header of `doc`, then the planes of `mask` (and with `tree` its tree
+// words, if it carries any) up to its segment count; one wait for the header,
+// one for all the copies -- and for what the caller enqueued before.
+int fetch_doc(mte_ctx* c, uint32_t doc, uint64_t mask, bool tree, DocFetch& f) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(&f.h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  f.n = (uint32_t)std::min<int64_t>(std::max(f.h.nseg, 0), c->cap);
+  f.mask = mask;
+  f.buf.assign((size_t)(__builtin_popcountll(mask) + 1) * f.n + 1, 0u);
+  const uint64_t db = (uint64_t)doc * c->cap;
+  const SegSoA& soa = c->docs.soa;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(soa.len) + db;
+  uint32_t* dst = f.buf.data();
+  for (int p = 0; p < 64 && f.n; p++)
+    if ((mask >> p) & 1u) {
+      HIPCHK(c, hipMemcpyAsync(dst, src + (uint64_t)p * soa.plane_stride, f.n * 4, hipMemcpyDeviceToHost, c->stream));
+      dst += f.n;
+    }
+  if (tree && f.n && doc_has_tree(c->docs.flags[doc]))
+    HIPCHK(c, hipMemcpyAsync(dst, c->docs.d_tree + db, f.n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MTE_OK;
+}
+
+// ... and the reference slots [0, n) of an MTE_DOC_REFS document (rt)
+int fetch_refs(mte_ctx* c, uint32_t doc, uint32_t n, std::vector<uint2>& rt, uint64_t mask, bool tree, DocFetch& f) {
+  if (!(c->docs.flags[doc] & MTE_DOC_REFS)) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
+  if (n > c->ref_cap) return set_err(c, MTE_E_INVALID_ARG, "%u reference slots > capacity %u", n, c->ref_cap);
+  HIPCHK(c, hipSetDevice(c->device));
+  rt.resize(n + 1);
+  if (n)
+    HIPCHK(c, hipMemcpyAsync(rt.data(), c->docs.d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
+                             hipMemcpyDeviceToHost, c->stream));
+  return fetch_doc(c, doc, mask, tree, f);
 }
 
 }  // namespace
@@ -1261,6 +1348,10 @@ int mte_destroy(mte_ctx* c) {
   return MTE_OK;
 }
 
+// All or nothing: a load refused for its arguments leaves the previous load as
+// it was; one that fails later (a HIP error, out of device memory) frees what
+// it built and leaves the context without documents, as if none had ever been
+// loaded -- mte_submit then takes no batch.
 int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const uint16_t* text,
                   uint64_t text_units, const mte_propset* propsets, uint32_t n_propsets,
                   const mte_prop* props, uint32_t n_props) {
@@ -1268,237 +1359,190 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
   JOIN_TAIL(c);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<uint32_t> iprops((size_t)n_docs * MTE_MAX_KEYS, 0u);
+  // One pass over docs[]: every argument check (nothing of the context changes
+  // before the last), each document's flags, initial properties and device
+  // description, and the launch lists by owner (doc_owner).
+  std::vector<uint32_t> flags(n_docs), iprops((size_t)n_docs * MTE_MAX_KEYS, 0u);
+  std::vector<mte_doc_init> dinit(docs, docs + n_docs);
+  std::vector<uint32_t> flat_docs, rs_docs, tree_docs, htree_docs, sdocs;
+  uint8_t key_text[MTE_MAX_KEYS] = {};  // the keys of the initial texts' properties
+  bool any_local = false, any_refs = false, any_maint = false;
   for (uint32_t d = 0; d < n_docs; d++) {
     const mte_doc_init& in = docs[d];
+    const uint32_t f = in.flags & kDocFlags;
+    const DocOwner own = doc_owner(f);
     if ((uint64_t)in.text_off + in.text_len > text_units || in.text_len > 0x7fffffffu)
       return set_err(c, MTE_E_INVALID_ARG, "doc %u: initial text out of range", d);
-    if ((in.flags & MTE_DOC_REFS) && !(in.flags & MTE_DOC_LOCAL_CLIENT))
+    if ((f & MTE_DOC_REFS) && !(f & MTE_DOC_LOCAL_CLIENT))
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: local references need MTE_DOC_LOCAL_CLIENT", d);
     // maintenance records come from the HBM tree pass, which keeps the
     // reference's segments (a local client's, MTE_DOC_TREE or a legacy document)
-    if ((in.flags & MTE_DOC_MAINT_EVENTS) &&
-        (!(in.flags & MTE_DOC_EVENTS) ||
-         !((in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) || !(in.flags & MTE_DOC_NEW_LENGTH_CALC))))
+    if ((f & MTE_DOC_MAINT_EVENTS) && !((f & MTE_DOC_EVENTS) && own == kOwnHtree))
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: maintenance events need MTE_DOC_EVENTS on the HBM tree pass "
                      "(MTE_DOC_LOCAL_CLIENT, MTE_DOC_TREE or the legacy length calculation)", d);
-    if ((in.flags & MTE_DOC_TREE) && (in.flags & MTE_DOC_ROUND_SYNC))
+    if ((f & MTE_DOC_TREE) && (f & MTE_DOC_ROUND_SYNC))
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: MTE_DOC_TREE with MTE_DOC_ROUND_SYNC", d);
     // delta events of a new length-calc document without a local client come
     // from the HBM-streamed flat pass, which big-document contexts do not run
-    if ((in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS | MTE_DOC_TREE)) == MTE_DOC_EVENTS &&
-        (in.flags & MTE_DOC_NEW_LENGTH_CALC) && c->cap >= kChunkMinCap)
+    if (own == kOwnStream && c->cap >= kChunkMinCap)
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: delta events of a document without a local client need a "
                      "context below %u segments", d, kChunkMinCap);
-    if ((in.flags & MTE_DOC_ROUND_SYNC) && (in.flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS)))
+    if ((f & MTE_DOC_ROUND_SYNC) && (f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS)))
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: MTE_DOC_ROUND_SYNC with a local client or delta events", d);
     if (in.propset != MTE_NO_PROPS) {
       if (in.propset >= n_propsets || !propsets) return set_err(c, MTE_E_INVALID_ARG, "doc %u: bad propset", d);
       const mte_propset ps = propsets[in.propset];
       if ((uint64_t)ps.first + ps.count > n_props) return set_err(c, MTE_E_INVALID_ARG, "doc %u: bad propset", d);
       for (uint32_t t = 0; t < ps.count; t++) {
-        const mte_prop p = props[ps.first + t];
-        if (p.key < c->n_keys) iprops[(size_t)d * MTE_MAX_KEYS + p.key] = p.value;
+        const mte_prop q = props[ps.first + t];
+        if (q.key < c->n_keys) iprops[(size_t)d * MTE_MAX_KEYS + q.key] = q.value;
+        if (q.key < MTE_MAX_KEYS) key_text[q.key] = 1;
       }
     }
+    const uint16_t* t0 = text + in.text_off;
+    dinit[d].flags = (in.flags & ~kInitNl) | (std::find(t0, t0 + in.text_len, 0x0A) != t0 + in.text_len ? kInitNl : 0u);
+    flags[d] = f;
+    any_local = any_local || (f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE));
+    any_refs = any_refs || (f & MTE_DOC_REFS);
+    any_maint = any_maint || (f & MTE_DOC_MAINT_EVENTS);
+    switch (own) {
+      case kOwnHtree: htree_docs.push_back(d); break;
+      case kOwnStream: sdocs.push_back(d); break;  // BatchSlot::sorder
+      case kOwnFlat: flat_docs.push_back(d); break;
+      case kOwnFlatRs: flat_docs.push_back(d), rs_docs.push_back(d); break;
+      case kOwnTree: tree_docs.push_back(d); break;
+    }
   }
+  // the HBM tree pass takes its own documents and the legacy ones the register
+  // tiers hand over (past 1,020 items, or from a batch with relative positions)
+  htree_docs.insert(htree_docs.end(), tree_docs.begin(), tree_docs.end());
+  for (uint32_t i = 0; propsets && i < n_propsets; i++)  // mte_load_segments indexes with these
+    if ((uint64_t)propsets[i].first + propsets[i].count > (props ? n_props : 0u))
+      return set_err(c, MTE_E_INVALID_ARG, "bad load propset");
   free_docs(c);
-  c->docs.n_docs = n_docs;
   c->submitted = false;
-  for (uint32_t k = 0; k < MTE_MAX_KEYS; k++) c->max_vid_k[k] = 0, c->key_text[k] = 0;
-  for (uint32_t i = 0; props && i < n_props; i++)
-    if (props[i].key < MTE_MAX_KEYS) c->max_vid_k[props[i].key] = std::max(c->max_vid_k[props[i].key], props[i].value);
-  for (uint32_t d = 0; d < n_docs; d++)  // the initial text's properties
-    if (docs[d].propset != MTE_NO_PROPS) {
-      const mte_propset ps = propsets[docs[d].propset];
-      for (uint32_t t = 0; t < ps.count; t++)
-        if (props[ps.first + t].key < MTE_MAX_KEYS) c->key_text[props[ps.first + t].key] = 1;
+  DocState& ds = c->docs;
+  // the load itself; on a failure what it built so far is dropped below
+  const int rc = [&]() -> int {
+    ds.n_docs = n_docs;
+    for (uint32_t k = 0; k < MTE_MAX_KEYS; k++) c->max_vid_k[k] = 0, c->key_text[k] = key_text[k];
+    for (uint32_t i = 0; props && i < n_props; i++)
+      if (props[i].key < MTE_MAX_KEYS)
+        c->max_vid_k[props[i].key] = std::max(c->max_vid_k[props[i].key], props[i].value);
+    c->ev_slot = -1;  // nothing of an earlier batch is reachable until the next mte_submit
+    for (BatchSlot& s : c->slot) s.n_ops = 0;
+    const uint64_t nslots = (uint64_t)(n_docs ? n_docs : 1) * c->cap;
+    ds.soa.plane_stride = nslots;
+    ds.flags = std::move(flags);
+    ds.h_sdocs = std::move(sdocs);
+    ds.any_maint = any_maint;
+    ds.h_ref_hi.assign(n_docs, 0);
+    if (any_refs) MTECHK(doc_alloc(c, &ds.d_refs, (uint64_t)c->ref_cap * n_docs));
+    // documents with a local client hold 2 kt + 6 more planes (mte_htree.h): the
+    // pending property keys, the annotate-group mask, the keys' values before
+    // their first pending annotate, localRemovedSeq, the removal-group order, the
+    // first group an item is one of the marked segments of, the regeneration
+    // group, the removers of short ids 32 .. 63 (the last one MTE_DOC_TREE
+    // documents use too)
+    uint64_t prop_planes = c->kt ? c->kt : 1;
+    if (any_local) prop_planes += local_planes((int)c->kt) - kFieldPlanes - c->kt;
+    MTECHK(doc_alloc(c, &ds.hdr, n_docs));
+    // one allocation, planes at stride nslots: len seq rseq rmask meta toff props[kt]
+    // (kt >= n_keys planes, so the register-resident kernels never index past it)
+    {
+      uint32_t* base = nullptr;
+      MTECHK(doc_alloc(c, &base, nslots * (kFieldPlanes + prop_planes)));
+      ds.soa.len = (int32_t*)base;
+      ds.soa.seq = (int32_t*)(base + 1 * nslots);
+      ds.soa.rseq = (int32_t*)(base + 2 * nslots);
+      ds.soa.rmask = base + 3 * nslots;
+      ds.soa.meta = base + 4 * nslots;
+      ds.soa.toff = base + 5 * nslots;
+      ds.soa.props = base + kFieldPlanes * nslots;
     }
-  c->ev_slot = -1;  // nothing of an earlier batch is reachable until the next mte_submit
-  for (BatchSlot& s : c->slot) s.n_ops = 0;
-  const uint64_t nslots = (uint64_t)(n_docs ? n_docs : 1) * c->cap;
-  c->docs.soa.plane_stride = nslots;
-  c->docs.h_local.assign(n_docs, 0);
-  c->docs.h_events.assign(n_docs, 0);
-  c->docs.h_refs.assign(n_docs, 0);
-  c->docs.h_slides.assign(n_docs, 0);
-  for (uint32_t d = 0; d < n_docs; d++)
-    if (docs[d].flags & MTE_DOC_MAINT_EVENTS) c->docs.any_maint = true;
-  c->docs.h_ref_hi.assign(n_docs, 0);
-  bool any_local = false, any_refs = false;
-  for (uint32_t d = 0; d < n_docs; d++) {
-    // the flat HBM-streamed pass's own: new length-calc documents with delta events and no local client
-    if ((docs[d].flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_TREE)) ==
-        (MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC))
-      c->docs.h_sdocs.push_back(d);
-    if (docs[d].flags & MTE_DOC_LOCAL_CLIENT) c->docs.h_local[d] = 1, any_local = true;
-    else if (docs[d].flags & MTE_DOC_TREE) c->docs.h_local[d] = 2, any_local = true;
-    if (docs[d].flags & MTE_DOC_EVENTS) c->docs.h_events[d] = 1;
-    if (docs[d].flags & MTE_DOC_REFS) c->docs.h_refs[d] = 1, any_refs = true;
-    const uint32_t sl = MTE_DOC_REFS | MTE_DOC_EVENTS | MTE_DOC_SLIDE_EVENTS;
-    if ((docs[d].flags & sl) == sl) c->docs.h_slides[d] = 1;
-  }
-  if (any_refs) HIPCHK(c, hipMalloc((void**)&c->docs.d_refs, sizeof(uint2) * (size_t)c->ref_cap * n_docs));
-  // documents with a local client hold 2 kt + 6 more planes (mte_htree.h): the
-  // pending property keys, the annotate-group mask, the keys' values before
-  // their first pending annotate, localRemovedSeq, the removal-group order, the
-  // first group an item is one of the marked segments of, the regeneration
-  // group, the removers of short ids 32 .. 63 (the last one MTE_DOC_TREE
-  // documents use too)
-  const uint64_t prop_planes = (c->kt ? c->kt : 1) + (any_local ? 2 * c->kt + 6 : 0);
-  HIPCHK(c, hipMalloc((void**)&c->docs.hdr, sizeof(DocHdr) * (n_docs ? n_docs : 1)));
-  // one allocation, planes at stride nslots: len seq rseq rmask meta toff props[kt]
-  // (kt >= n_keys planes, so the register-resident kernels never index past it)
-  {
-    const uint64_t planes = kFieldPlanes + prop_planes;
-    uint32_t* base = nullptr;
-    HIPCHK(c, hipMalloc((void**)&base, nslots * 4 * planes));
-    c->docs.soa.len = (int32_t*)base;
-    c->docs.soa.seq = (int32_t*)(base + 1 * nslots);
-    c->docs.soa.rseq = (int32_t*)(base + 2 * nslots);
-    c->docs.soa.rmask = base + 3 * nslots;
-    c->docs.soa.meta = base + 4 * nslots;
-    c->docs.soa.toff = base + 5 * nslots;
-    c->docs.soa.props = base + kFieldPlanes * nslots;
-  }
-  HIPCHK(c, hipMemsetAsync(c->docs.soa.props, 0, nslots * 4 * prop_planes, c->stream));
-  if (c->cap >= kChunkMinCap && n_docs) {
-    // chunk arena: every doc can be re-laid out at kChFill segments per chunk
-    const uint32_t nch_cap = c->cap / kChFill + 2;
-    const uint32_t ng_cap = (nch_cap + kChGroup - 1) / kChGroup;
-    if (ng_cap <= kChMaxGroups) {
-      ChunkArgs& ch = c->docs.ch;
-      ch.nch_cap = nch_cap;
-      ch.ng_cap = ng_cap;
-      const uint64_t nch_all = (uint64_t)n_docs * nch_cap;
-      ch.astride = nch_all * kChSlots;
-      const uint64_t planes = kFieldPlanes + (c->kt ? c->kt : 1);
-      HIPCHK(c, hipMalloc((void**)&ch.arena, ch.astride * 4 * planes));
-      HIPCHK(c, hipMalloc((void**)&ch.cnt, nch_all * 4));
-      HIPCHK(c, hipMalloc((void**)&ch.kc, nch_all * 4));
-      HIPCHK(c, hipMalloc((void**)&ch.sum, nch_all * 4 * MTE_MAX_CLIENTS));
-      RoundArgs& rd = c->docs.rd;
-      HIPCHK(c, hipMalloc((void**)&rd.plan, sizeof(uint4) * n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.acct, sizeof(unsigned long long) * n_docs));
-      HIPCHK(c, hipMemsetAsync(rd.acct, 0, sizeof(unsigned long long) * n_docs, c->stream));
-      HIPCHK(c, hipMalloc((void**)&rd.rcnt, nch_all * 4));
-      HIPCHK(c, hipMalloc((void**)&rd.rbuf, nch_all * kRB * sizeof(uint2)));
-      HIPCHK(c, hipMalloc((void**)&rd.rrec, nch_all * kRB * 2 * sizeof(uint4)));
-      HIPCHK(c, hipMalloc((void**)&rd.rflag, 4 * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.nch, 4 * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.nnew, 4 * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.rchain, sizeof(uint2) * MTE_MAX_CLIENTS * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.live, 4 * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.gfl, 4 * (uint64_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&rd.count, 16));
-      if (!c->h_rcount) HIPCHK(c, hipHostMalloc((void**)&c->h_rcount, 16, 0));
-      c->docs.chunked = true;
-    }
-  }
-  HIPCHK(c, hipMalloc((void**)&c->docs.stats, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1)));
-  HIPCHK(c, hipMemsetAsync(c->docs.stats, 0, sizeof(unsigned long long) * kNumStats * (n_docs ? n_docs : 1), c->stream));
-  HIPCHK(c, hipMalloc((void**)&c->docs.d_inits, sizeof(mte_doc_init) * (n_docs ? n_docs : 1)));
-  HIPCHK(c, hipMalloc((void**)&c->docs.d_init_props, sizeof(uint32_t) * iprops.size() + 4));
-  HIPCHK(c, hipMalloc((void**)&c->docs.d_digest, sizeof(uint64_t) * 4 * (n_docs ? n_docs : 1)));
-  {
-    // pass-1 groups: g consecutive documents per wave, g the smallest count
-    // that puts the whole batch on the chip at once (CUs x 4 SIMDs x
-    // pass1_waves() waves), so a batch that fits at one document per wave
-    // (config 2's 1k docs, the 1,250 per GPU of an 8-GPU 10k job) runs one per
-    // wave: grouping it would leave SIMDs idle and serialise its documents.
-    // Legacy length-calc documents go to the tree pass instead (mte_tree.h).
-    // Round-synchronous legacy documents (MTE_DOC_ROUND_SYNC) stay flat, behind
-    // the per-batch check of round_sync_kernel.
-    std::vector<uint32_t> flat_docs, tree_docs, rs_docs, htree_docs;
-    c->docs.h_legacy.assign(n_docs, 0);  // the document carries tree words (read-outs join merged leaves)
-    for (uint32_t d = 0; d < n_docs; d++) {
-      const uint32_t f = docs[d].flags;
-      if ((f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) || ((f & MTE_DOC_EVENTS) && !(f & MTE_DOC_NEW_LENGTH_CALC))) {
-        htree_docs.push_back(d);  // the HBM tree pass's own (mte_htree.h)
-        c->docs.h_legacy[d] = 1;
-      } else if (f & MTE_DOC_EVENTS) {
-        continue;  // the HBM-streamed flat pass replays them (mte_stream.h)
-      } else if (docs[d].flags & MTE_DOC_NEW_LENGTH_CALC) {
-        flat_docs.push_back(d);
-      } else if (docs[d].flags & MTE_DOC_ROUND_SYNC) {
-        flat_docs.push_back(d);
-        rs_docs.push_back(d);
-      } else {
-        tree_docs.push_back(d);
-        c->docs.h_legacy[d] = 1;
+    HIPCHK(c, hipMemsetAsync(ds.soa.props, 0, nslots * 4 * prop_planes, c->stream));
+    if (c->cap >= kChunkMinCap && n_docs) {
+      // chunk arena: every doc can be re-laid out at kChFill segments per chunk
+      const uint32_t nch_cap = c->cap / kChFill + 2;
+      const uint32_t ng_cap = (nch_cap + kChGroup - 1) / kChGroup;
+      if (ng_cap <= kChMaxGroups) {
+        ChunkArgs& ch = ds.ch;
+        ch.nch_cap = nch_cap;
+        ch.ng_cap = ng_cap;
+        const uint64_t nch_all = (uint64_t)n_docs * nch_cap;
+        ch.astride = nch_all * kChSlots;
+        MTECHK(doc_alloc(c, &ch.arena, ch.astride * (kFieldPlanes + (c->kt ? c->kt : 1))));
+        RoundArgs& rd = ds.rd;
+        for (uint32_t** q : {&ch.cnt, &ch.kc, &rd.rcnt}) MTECHK(doc_alloc(c, q, nch_all));
+        for (uint32_t** q : {&rd.rflag, &rd.nch, &rd.nnew, &rd.live, &rd.gfl}) MTECHK(doc_alloc(c, q, n_docs));
+        MTECHK(doc_alloc(c, &ch.sum, nch_all * MTE_MAX_CLIENTS));
+        MTECHK(doc_alloc(c, &rd.plan, n_docs));
+        MTECHK(doc_alloc(c, &rd.acct, n_docs, true));
+        MTECHK(doc_alloc(c, &rd.rbuf, nch_all * kRB));
+        MTECHK(doc_alloc(c, &rd.rrec, nch_all * kRB * 2));
+        MTECHK(doc_alloc(c, &rd.rchain, (uint64_t)MTE_MAX_CLIENTS * n_docs));
+        MTECHK(doc_alloc(c, &rd.count, 4));
+        if (!c->h_rcount) HIPCHK(c, hipHostMalloc((void**)&c->h_rcount, 16, 0));
+        ds.chunked = true;
       }
     }
-    const uint32_t nf = (uint32_t)flat_docs.size();
-    int n_cu = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) n_cu = 0;
-    const uint64_t resident = (n_cu > 0 ? (uint64_t)n_cu : 256) * 4 * (uint64_t)pass1_waves();
-    const uint32_t g = (uint32_t)std::min<uint64_t>(kGroupMax, std::max<uint64_t>(1, (nf + resident - 1) / resident));
-    c->docs.pass1_group = g;
-    c->docs.n_pairs = (nf + g - 1) / g;
-    std::vector<uint32_t> pairs((size_t)c->docs.n_pairs * g + g, 0xffffffffu);
-    for (uint32_t i = 0; i < nf; i++) pairs[i] = flat_docs[i];
-    HIPCHK(c, hipMalloc((void**)&c->docs.d_pairs, pairs.size() * 4));
-    HIPCHK(c, hipMemcpy(c->docs.d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
-    c->docs.n_rs = (uint32_t)rs_docs.size();
-    if (c->docs.n_rs) {
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_rs_docs, rs_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->docs.d_rs_docs, rs_docs.data(), rs_docs.size() * 4, hipMemcpyHostToDevice));
+    MTECHK(doc_alloc(c, &ds.stats, (uint64_t)kNumStats * n_docs, true));
+    MTECHK(doc_upload(c, &ds.d_inits, dinit));
+    MTECHK(doc_upload(c, &ds.d_init_props, iprops));
+    MTECHK(doc_alloc(c, &ds.d_digest, 4ull * n_docs));
+    {
+      // pass-1 groups: g consecutive documents per wave, g the smallest count
+      // that puts the whole batch on the chip at once (CUs x 4 SIMDs x
+      // pass1_waves() waves), so a batch that fits at one document per wave
+      // (config 2's 1k docs, the 1,250 per GPU of an 8-GPU 10k job) runs one per
+      // wave: grouping it would leave SIMDs idle and serialise its documents.
+      const uint32_t nf = (uint32_t)flat_docs.size();
+      int n_cu = 0;
+      if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) n_cu = 0;
+      const uint64_t resident = (n_cu > 0 ? (uint64_t)n_cu : 256) * 4 * (uint64_t)pass1_waves();
+      const uint32_t g = (uint32_t)std::min<uint64_t>(kGroupMax, std::max<uint64_t>(1, (nf + resident - 1) / resident));
+      ds.pass1_group = g;
+      ds.n_pairs = (nf + g - 1) / g;
+      std::vector<uint32_t> pairs((size_t)ds.n_pairs * g + g, 0xffffffffu);
+      std::copy(flat_docs.begin(), flat_docs.end(), pairs.begin());
+      MTECHK(doc_upload(c, &ds.d_pairs, pairs));
     }
-    c->docs.n_tree = (uint32_t)tree_docs.size();
-    if (c->docs.n_tree) {
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_heap, sizeof(uint2) * (kTreeHeapCap + 1) * (size_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_tree_docs, tree_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->docs.d_tree_docs, tree_docs.data(), tree_docs.size() * 4, hipMemcpyHostToDevice));
+    ds.n_rs = (uint32_t)rs_docs.size();
+    if (ds.n_rs) MTECHK(doc_upload(c, &ds.d_rs_docs, rs_docs));
+    ds.n_tree = (uint32_t)tree_docs.size();
+    if (ds.n_tree) {
+      MTECHK(doc_alloc(c, &ds.d_heap, (uint64_t)(kTreeHeapCap + 1) * n_docs));
+      MTECHK(doc_upload(c, &ds.d_tree_docs, tree_docs));
     }
-    // the HBM tree pass takes its own documents and the legacy ones the
-    // register tiers hand over (past 1,020 items, or from a batch with
-    // relative positions)
-    for (uint32_t d : tree_docs) htree_docs.push_back(d);
-    c->docs.n_htree = (uint32_t)htree_docs.size();
-    if (c->docs.n_tree || c->docs.n_htree) {
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_tree, nslots * 4));
-      HIPCHK(c, hipMemsetAsync(c->docs.d_tree, 0, nslots * 4, c->stream));
+    ds.n_htree = (uint32_t)htree_docs.size();  // the tree pass's documents among them
+    if (ds.n_htree) {
+      MTECHK(doc_alloc(c, &ds.d_tree, nslots, true));
+      ds.hcap = c->cap;  // one heap entry per slot
+      MTECHK(doc_alloc(c, &ds.d_hheap, ((uint64_t)ds.hcap + 1) * n_docs));
+      MTECHK(doc_alloc(c, &ds.d_hst, (uint64_t)kHtState * n_docs));
+      MTECHK(doc_alloc(c, &ds.d_hscr, 2 * nslots));
+      MTECHK(doc_upload(c, &ds.d_htree_docs, htree_docs));
+      ds.h_htree_docs = std::move(htree_docs);
     }
-    if (c->docs.n_htree) {
-      c->docs.hcap = c->cap;  // one heap entry per slot
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_hheap, sizeof(uint2) * ((size_t)c->docs.hcap + 1) * n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_hst, sizeof(uint32_t) * kHtState * (size_t)n_docs));
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_hscr, sizeof(int32_t) * 2 * nslots));
-      c->docs.h_htree_docs = htree_docs;
-      HIPCHK(c, hipMalloc((void**)&c->docs.d_htree_docs, htree_docs.size() * 4));
-      HIPCHK(c, hipMemcpy(c->docs.d_htree_docs, htree_docs.data(), htree_docs.size() * 4, hipMemcpyHostToDevice));
-    }
+    c->h_load_ps.assign(propsets, propsets + (propsets ? n_propsets : 0));
+    c->h_load_pe.assign(props, props + (props ? n_props : 0));
+    // text arena restarts with the load text
+    c->arena_n = 0;
+    c->h_arena.assign(text, text + text_units);
+    MTECHK(grow(c, c->arena, text_units + 1));
+    if (text_units)
+      HIPCHK(c, hipMemcpyAsync(c->arena.p, text, text_units * 2, hipMemcpyHostToDevice, c->stream));
+    c->arena_n = text_units;
+    MTECHK(launch_reset(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MTE_OK;
+  }();
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);  // the clears and copies enqueued so far
+    (void)hipGetLastError();                // the failure is reported in rc
+    free_docs(c);
   }
-  if (n_docs) {
-    std::vector<mte_doc_init> dinit(docs, docs + n_docs);
-    for (mte_doc_init& di : dinit) {
-      di.flags &= ~kInitNl;
-      for (uint32_t u = 0; u < di.text_len; u++)
-        if (text[di.text_off + u] == 0x0A) {
-          di.flags |= kInitNl;
-          break;
-        }
-    }
-    HIPCHK(c, hipMemcpy(c->docs.d_inits, dinit.data(), sizeof(mte_doc_init) * n_docs, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpyAsync(c->docs.d_init_props, iprops.data(), sizeof(uint32_t) * iprops.size(),
-                             hipMemcpyHostToDevice, c->stream));
-  }
-  c->h_load_ps.assign(propsets, propsets + (propsets ? n_propsets : 0));
-  c->h_load_pe.assign(props, props + (props ? n_props : 0));
-  for (const mte_propset& ps : c->h_load_ps)
-    if ((uint64_t)ps.first + ps.count > c->h_load_pe.size()) return set_err(c, MTE_E_INVALID_ARG, "bad load propset");
-  // text arena restarts with the load text
-  c->arena_n = 0;
-  c->h_arena.assign(text, text + text_units);
-  int rc = grow(c, c->arena, text_units + 1);
-  if (rc) return rc;
-  if (text_units)
-    HIPCHK(c, hipMemcpyAsync(c->arena.p, text, text_units * 2, hipMemcpyHostToDevice, c->stream));
-  c->arena_n = text_units;
-  rc = launch_reset(c);
-  if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MTE_OK;
+  return rc;
 }
 
 int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* segs, uint64_t n_segs) {
@@ -1535,7 +1579,8 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
       img[4 * n_segs + g] = (uint32_t)(sg.client + 1) | (sg.kind << 8);
       // a marker of an MTE_DOC_REFS document is named by its index in the load
       // (above every arena offset), as an inserted one by its reserved unit
-      img[5 * n_segs + g] = marker ? (c->docs.h_refs[d] ? 0x80000000u + (uint32_t)(g - b) : 0u) : sg.text_off;
+      img[5 * n_segs + g] =
+          marker ? ((c->docs.flags[d] & MTE_DOC_REFS) ? 0x80000000u + (uint32_t)(g - b) : 0u) : sg.text_off;
       {
         const uint64_t nd = e - b, k = g - b;
         int depth = 1;
@@ -1578,15 +1623,17 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
       c->docs.image.uc.val[p] = v[0];
     }
   }
-  HIPCHK(c, hipMalloc((void**)&c->docs.image.img, img.size() * 4));
-  HIPCHK(c, hipMalloc((void**)&c->docs.image.doc, doc.size() * 4));
-  HIPCHK(c, hipMalloc((void**)&c->docs.image.off, ((size_t)c->docs.n_docs + 1) * 8));
-  HIPCHK(c, hipMemcpy(c->docs.image.img, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->docs.image.doc, doc.data(), doc.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->docs.image.off, seg_offsets, ((size_t)c->docs.n_docs + 1) * 8, hipMemcpyHostToDevice));
-  c->docs.image.n = n_segs;
-  int rc = launch_reset(c);
-  if (rc) return rc;
+  SegImage& im = c->docs.image;
+  const uint64_t n_off = (uint64_t)c->docs.n_docs + 1;
+  // sized exactly (grow() would round a big-document image up to twice its size)
+  HIPCHK(c, hipMalloc((void**)&im.img.p, (im.img.cap = img.size()) * 4));
+  HIPCHK(c, hipMalloc((void**)&im.doc.p, (im.doc.cap = doc.size()) * 4));
+  HIPCHK(c, hipMalloc((void**)&im.off.p, (im.off.cap = n_off) * 8));
+  HIPCHK(c, hipMemcpy(im.img.p, img.data(), img.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(im.doc.p, doc.data(), doc.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(im.off.p, seg_offsets, n_off * 8, hipMemcpyHostToDevice));
+  im.n = n_segs;
+  MTECHK(launch_reset(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MTE_OK;
 }
@@ -1594,8 +1641,17 @@ int mte_load_segments(mte_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
 int mte_submit(mte_ctx* c, const mte_batch* b) {
   if (!c || !b || b->n_docs != c->docs.n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
   if (b->op_offsets[0] != 0 || b->op_offsets[b->n_docs] != b->n_ops) return set_err(c, MTE_E_INVALID_ARG, "op_offsets");
-  for (uint32_t d = 0; d < b->n_docs; d++)
+  uint64_t max_doc_ops = 0;
+  for (uint32_t d = 0; d < b->n_docs; d++) {
     if (b->op_offsets[d + 1] < b->op_offsets[d]) return set_err(c, MTE_E_INVALID_ARG, "op_offsets not sorted");
+    max_doc_ops = std::max<uint64_t>(max_doc_ops, b->op_offsets[d + 1] - b->op_offsets[d]);
+  }
+  // most records first: the long chains start first (stable: equal counts keep the list's order)
+  const auto by_ops = [b](std::vector<uint32_t>& docs) {
+    std::stable_sort(docs.begin(), docs.end(), [b](uint32_t x, uint32_t y) {
+      return b->op_offsets[x + 1] - b->op_offsets[x] > b->op_offsets[y + 1] - b->op_offsets[y];
+    });
+  };
   for (uint32_t i = 0; i < b->n_propsets; i++)
     if ((uint64_t)b->propsets[i].first + b->propsets[i].count > b->n_props)
       return set_err(c, MTE_E_INVALID_ARG, "propset %u out of range", i);
@@ -1651,9 +1707,7 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
                              c->up_stream));
   if (!c->docs.h_sdocs.empty()) {
     std::vector<uint32_t> order(c->docs.h_sdocs);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-      return b->op_offsets[x + 1] - b->op_offsets[x] > b->op_offsets[y + 1] - b->op_offsets[y];
-    });
+    by_ops(order);
     std::vector<uint8_t> in(b->n_docs, 0);
     for (uint32_t d : order) in[d] = 1;
     for (uint32_t d = 0; d < b->n_docs; d++)
@@ -1664,12 +1718,10 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
     HIPCHK(c, hipStreamSynchronize(c->up_stream));  // `order` goes out of scope
   }
   if (!c->docs.h_htree_docs.empty()) {
-    // the HBM tree pass's documents, most records first (the long chains start first)
+    // the HBM tree pass's documents, most records first
     std::vector<uint32_t>& ho = c->h_hord;
     ho = c->docs.h_htree_docs;
-    std::stable_sort(ho.begin(), ho.end(), [&](uint32_t x, uint32_t y) {
-      return b->op_offsets[x + 1] - b->op_offsets[x] > b->op_offsets[y + 1] - b->op_offsets[y];
-    });
+    by_ops(ho);
     if ((rc = grow(c, s.hord, (uint64_t)ho.size()))) return rc;
     HIPCHK(c, hipMemcpyAsync(s.hord.p, ho.data(), ho.size() * 4, hipMemcpyHostToDevice, c->up_stream));
   }
@@ -1688,10 +1740,11 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
     off.assign((size_t)b->n_docs + 1, 0);
     bool any = false;
     for (uint32_t d = 0; d < b->n_docs; d++) {
-      const bool e = d < c->docs.h_events.size() && c->docs.h_events[d];
+      const uint32_t f = c->docs.flags[d];
+      const bool e = (f & MTE_DOC_EVENTS) != 0;
       any = any || e;
       uint64_t extra = 0;
-      if (e && d < c->docs.h_slides.size() && c->docs.h_slides[d]) {
+      if (e && (f & MTE_DOC_REFS) && (f & MTE_DOC_SLIDE_EVENTS)) {
         uint32_t hi = c->docs.h_ref_hi[d];
         uint64_t sliding = 0;
         for (uint64_t i = b->op_offsets[d]; i < b->op_offsets[d + 1]; i++) {
@@ -1727,9 +1780,7 @@ int mte_submit(mte_ctx* c, const mte_batch* b) {
     }
   s.n_ops = b->n_ops;
   s.n_propsets = b->n_propsets;
-  uint64_t mx = 0;
-  for (uint32_t d = 0; d < b->n_docs; d++) mx = std::max<uint64_t>(mx, b->op_offsets[d + 1] - b->op_offsets[d]);
-  s.max_doc_ops = mx;
+  s.max_doc_ops = max_doc_ops;
   c->rslot = w;
   c->submitted = true;
   return MTE_OK;
@@ -1789,7 +1840,7 @@ int mte_run(mte_ctx* c) {
   }
   a.eta = (unsigned long long)(eta_ms * 1e5);
   if (c->wclock_path) {
-    if (!c->docs.d_wclock) HIPCHK(c, hipMalloc((void**)&c->docs.d_wclock, 16ull * (c->docs.n_pairs + 1)));
+    if (!c->docs.d_wclock) MTECHK(doc_alloc(c, &c->docs.d_wclock, 2ull * (c->docs.n_pairs + 1)));
     a.wclock = c->docs.d_wclock;
   }
   if (c->docs.n_rs) {
@@ -1809,13 +1860,7 @@ int mte_run(mte_ctx* c) {
                        (uint32_t)s.n_propsets, s.pe.p, c->n_keys, side, pack, s.cps.p);
     HIPCHK(c, hipGetLastError());
   }
-  int rc;
-  if (c->stats_on)
-    rc = c->kt == 0 ? launch_replay<0, true>(c, a) : (c->kt == 4 ? launch_replay<4, true>(c, a) : launch_replay<8, true>(c, a));
-  else
-    rc = c->kt == 0 ? launch_replay<0, false>(c, a)
-                    : (c->kt == 4 ? launch_replay<4, false>(c, a) : launch_replay<8, false>(c, a));
-  if (rc) return rc;
+  MTECHK(launch_replay_of(c, a));
   c->ran = true;
   const int slot = c->rslot;
   auto finish = [c, slot]() -> int {
@@ -1884,14 +1929,13 @@ int mte_digest_device(mte_ctx* c, void* out, uint32_t n_docs) {
   a.out = (uint64_t*)out;
   if (c->cap > kDgWaveMaxCap) {
     // documents of up to `cap` segments: tile-parallel (dg_*_kernel)
-    if (!c->docs.d_dgt) {
+    if (!c->docs.dgt.tot) {  // the last of the three
       DigestTiles& t = c->docs.dgt;
       t.tpd = (c->cap + kDgTile - 1) / kDgTile;
       const uint64_t nt = (uint64_t)c->docs.n_docs * t.tpd;
-      HIPCHK(c, hipMalloc(&c->docs.d_dgt, nt * (4 + 24) + 4ull * c->docs.n_docs + 64));
-      t.part = (uint64_t*)c->docs.d_dgt;
-      t.tsum = (int32_t*)(t.part + 3 * nt);
-      t.tot = t.tsum + nt;
+      MTECHK(doc_alloc(c, &t.part, 3 * nt));
+      MTECHK(doc_alloc(c, &t.tsum, nt));
+      MTECHK(doc_alloc(c, &t.tot, c->docs.n_docs));
     }
     const uint64_t nt = (uint64_t)n_docs * c->docs.dgt.tpd;
     const uint32_t tb = (uint32_t)((nt + 3) / 4);
@@ -1932,30 +1976,14 @@ int mte_doc_status(mte_ctx* c, int32_t* out, uint32_t n_docs) {
 int mte_read_doc(mte_ctx* c, uint32_t doc, mte_doc_view* v) {
   if (!c || !v || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  HIPCHK(c, hipSetDevice(c->device));
-  DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t n = (uint32_t)std::max(h.nseg, 0);
-  const uint64_t db = (uint64_t)doc * c->cap;
-  std::vector<int32_t> len(n + 1), rseq(n + 1);
-  std::vector<uint32_t> meta(n + 1), toff(n + 1), props((size_t)(n + 1) * (c->n_keys ? c->n_keys : 1));
-  std::vector<uint32_t> tw(n + 1, 0u);  // tree words (legacy documents)
-  if (n && c->docs.d_tree && c->docs.h_legacy[doc])
-    HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (n) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->docs.soa.rseq + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(meta.data(), c->docs.soa.meta + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-    for (uint32_t k = 0; k < c->n_keys; k++)
-      HIPCHK(c, hipMemcpyAsync(props.data() + (size_t)k * n, c->docs.soa.props + k * c->docs.soa.plane_stride + db, n * 4,
-                               hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  v->status = h.status;
-  v->cur_seq = h.cur_seq;
-  v->min_seq = h.min_seq;
+  DocFetch f;
+  MTECHK(fetch_doc(c, doc, plane_set(kPlLen) | plane_set(kPlRseq) | plane_set(kPlMeta, 2 + (int)c->n_keys), true, f));
+  const uint32_t n = f.n;
+  const int32_t *len = f.iplane(kPlLen), *rseq = f.iplane(kPlRseq);
+  const uint32_t *meta = f.plane(kPlMeta), *toff = f.plane(kPlToff), *tw = f.tree();
+  v->status = f.h.status;
+  v->cur_seq = f.h.cur_seq;
+  v->min_seq = f.h.min_seq;
   uint32_t length = 0, nt = 0, ns = 0;
   for (uint32_t i = 0; i < n; i++) {
     if (rseq[i] != kNone) continue;  // gatherText: only segments not removed
@@ -1967,7 +1995,8 @@ int mte_read_doc(mte_ctx* c, uint32_t doc, mte_doc_view* v) {
         if (v->seg_len) v->seg_len[ns] = (uint32_t)len[i];
         if (v->seg_kind) v->seg_kind[ns] = kind;
         if (v->seg_props)
-          for (uint32_t k = 0; k < c->n_keys; k++) v->seg_props[(size_t)ns * c->n_keys + k] = props[(size_t)k * n + i];
+          for (uint32_t k = 0; k < c->n_keys; k++)
+            v->seg_props[(size_t)ns * c->n_keys + k] = f.plane(kFieldPlanes + (int)k)[i];
       }
       ns++;
     }
@@ -2007,38 +2036,21 @@ int mte_set_ref_capacity(mte_ctx* c, uint32_t per_doc) {
 static int read_refs_view(mte_ctx* c, uint32_t doc, int32_t* pos, uint32_t n, bool transient) {
   if (!c || (n && !pos) || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (c->docs.h_refs.empty() || !c->docs.h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
-  if (n > c->ref_cap) return set_err(c, MTE_E_INVALID_ARG, "%u reference slots > capacity %u", n, c->ref_cap);
-  HIPCHK(c, hipSetDevice(c->device));
-  DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t ns = (uint32_t)std::max(h.nseg, 0);
-  const uint64_t db = (uint64_t)doc * c->cap;
-  std::vector<int32_t> len(ns + 1), rseq(ns + 1);
-  std::vector<uint32_t> toff(ns + 1);
-  std::vector<uint2> rt(n + 1);
-  std::vector<uint32_t> tw;  // tree words, for Transient references (their leaf ids)
-  if (ns) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rseq.data(), c->docs.soa.rseq + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->docs.d_tree) {
-      tw.resize(ns);
-      HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-  }
-  if (n)
-    HIPCHK(c, hipMemcpyAsync(rt.data(), c->docs.d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
-                             hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint2> rt;
+  DocFetch f;
+  // the tree words are for Transient references (their leaf ids); a document
+  // with references has a local client, so it carries them
+  MTECHK(fetch_refs(c, doc, n, rt, plane_set(kPlLen) | plane_set(kPlRseq) | plane_set(kPlToff), true, f));
+  const uint32_t ns = f.n;
+  const int32_t *len = f.iplane(kPlLen), *rseq = f.iplane(kPlRseq);
+  const uint32_t *toff = f.plane(kPlToff), *tw = f.tree();
   for (uint32_t r = 0; r < n; r++) {
     pos[r] = -1;
     if ((rt[r].y & kRefLive) && (rt[r].y & kRefTrans)) {
       // a Transient reference: its segment (leaf id) + its offset, the offset
       // dropped once removed; -1 once the segment is gone (mergeTree.ts:1095-1112)
       int64_t p = 0;
-      for (uint32_t i = 0; i < ns && i < (uint32_t)tw.size(); i++) {
+      for (uint32_t i = 0; i < ns; i++) {
         const bool head = !(tw[i] & (kTCont | kTEmpty));
         if (head && ((tw[i] >> 8) & (kIdLimit - 1u)) == rt[r].x) {
           pos[r] = (int32_t)(p + (rseq[i] != kNone ? 0 : (int64_t)(rt[r].y & kRefTransOff)));
@@ -2070,25 +2082,12 @@ int mte_read_refs_transient(mte_ctx* c, uint32_t doc, int32_t* pos, uint32_t n) 
 int mte_read_ref_order(mte_ctx* c, uint32_t doc, int64_t* key, uint32_t n) {
   if (!c || (n && !key) || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  if (c->docs.h_refs.empty() || !c->docs.h_refs[doc]) return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_REFS", doc);
-  if (n > c->ref_cap) return set_err(c, MTE_E_INVALID_ARG, "%u reference slots > capacity %u", n, c->ref_cap);
-  HIPCHK(c, hipSetDevice(c->device));
-  DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t ns = (uint32_t)std::max(h.nseg, 0);
-  const uint64_t db = (uint64_t)doc * c->cap;
-  std::vector<int32_t> len(ns + 1);
-  std::vector<uint32_t> toff(ns + 1);
-  std::vector<uint2> rt(n + 1);
-  if (ns) {
-    HIPCHK(c, hipMemcpyAsync(len.data(), c->docs.soa.len + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(toff.data(), c->docs.soa.toff + db, ns * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  if (n)
-    HIPCHK(c, hipMemcpyAsync(rt.data(), c->docs.d_refs + (uint64_t)doc * c->ref_cap, n * sizeof(uint2),
-                             hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint2> rt;
+  DocFetch f;
+  MTECHK(fetch_refs(c, doc, n, rt, plane_set(kPlLen) | plane_set(kPlToff), false, f));
+  const uint32_t ns = f.n;
+  const int32_t* len = f.iplane(kPlLen);
+  const uint32_t* toff = f.plane(kPlToff);
   for (uint32_t r = 0; r < n; r++) {
     key[r] = -1;
     // a reference off the string still sits on its segment (compareReferencePositions
@@ -2110,7 +2109,7 @@ int mte_read_deltas(mte_ctx* c, uint32_t doc, mte_delta* out, uint64_t cap, uint
   if (!c || !n || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
   *n = 0;
-  if (c->docs.h_events.empty() || !c->docs.h_events[doc])
+  if (!(c->docs.flags[doc] & MTE_DOC_EVENTS))
     return set_err(c, MTE_E_INVALID_ARG, "doc %u: no MTE_DOC_EVENTS", doc);
   if (c->ev_slot < 0) return MTE_OK;  // no batch with events ran yet
   HIPCHK(c, hipSetDevice(c->device));
@@ -2130,32 +2129,17 @@ int mte_read_deltas(mte_ctx* c, uint32_t doc, mte_delta* out, uint64_t cap, uint
 int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
   if (!c || !v || doc >= c->docs.n_docs) return MTE_E_INVALID_ARG;
   JOIN_TAIL(c);
-  HIPCHK(c, hipSetDevice(c->device));
-  DocHdr h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->docs.hdr + doc, sizeof(DocHdr), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t n = (uint32_t)std::max(h.nseg, 0);
-  const uint64_t db = (uint64_t)doc * c->cap;
-  const uint32_t np = kFieldPlanes + c->n_keys;
-  std::vector<uint32_t> pl((size_t)np * (n + 1));
-  std::vector<uint32_t> tw(n + 1, 0u);
-  if (n && c->docs.d_tree && c->docs.h_legacy[doc])
-    HIPCHK(c, hipMemcpyAsync(tw.data(), c->docs.d_tree + db, n * 4, hipMemcpyDeviceToHost, c->stream));
-  for (uint32_t p = 0; p < np && n; p++)
-    HIPCHK(c, hipMemcpyAsync(pl.data() + (size_t)p * n, reinterpret_cast<const uint32_t*>(c->docs.soa.len) +
-                                                             p * c->docs.soa.plane_stride + db,
-                             n * 4, hipMemcpyDeviceToHost, c->stream));
-  // the removers of short ids >= 32 (mte_htree.h kRmHiPlane): mte_seg.removers has 32 bits
-  std::vector<uint32_t> rmh;
-  if (n && !c->docs.h_local.empty() && c->docs.h_local[doc]) {
-    rmh.resize(n);
-    HIPCHK(c, hipMemcpyAsync(rmh.data(), reinterpret_cast<const uint32_t*>(c->docs.soa.len) +
-                                             (uint64_t)(kFieldPlanes + 3 * c->kt + 5) * c->docs.soa.plane_stride + db,
-                             n * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (uint32_t i = 0; i < (uint32_t)rmh.size(); i++)
-    if (rmh[i] && !(tw[i] & kTEmpty) && (int32_t)pl[2 * (size_t)n + i] != kNone)
+  // the removers of short ids >= 32 (rm_hi_plane, of the documents with the
+  // local planes): mte_seg.removers has 32 bits
+  const bool rm_hi = (c->docs.flags[doc] & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) != 0;
+  const int rmp = rm_hi_plane((int)c->kt);
+  DocFetch f;
+  MTECHK(fetch_doc(c, doc, plane_set(0, kFieldPlanes + (int)c->n_keys) | (rm_hi ? plane_set(rmp) : 0u), true, f));
+  const uint32_t n = f.n;
+  const DocHdr& h = f.h;
+  const uint32_t* tw = f.tree();
+  for (uint32_t i = 0; rm_hi && i < n; i++)
+    if (f.plane(rmp)[i] && !(tw[i] & kTEmpty) && f.iplane(kPlRseq)[i] != kNone)
       return set_err(c, MTE_E_UNSUPPORTED, "doc %u: a segment removed by a short id >= 32 (mte_seg.removers)", doc);
   uint64_t nt = 0;
   uint64_t m = 0;  // segments out (a tree pass placeholder is none, a merged leaf one)
@@ -2166,15 +2150,14 @@ int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
   // reference's scour does in its own time, mergeTree.ts:681-747).  No later
   // op sees them and a summary leaves them out (snapshotV1.ts:195-199): the
   // list is the canonical one, without them.
-  const bool lazy_zamboni = c->docs.rounds_carried && !c->docs.h_legacy[doc];
+  const bool lazy_zamboni = c->docs.rounds_carried && !doc_has_tree(c->docs.flags[doc]);
   for (uint32_t i = 0; i < n; i++) {
-    const int32_t len = (int32_t)pl[i], rseq = (int32_t)pl[2 * (size_t)n + i];
-    const uint32_t meta = pl[4 * (size_t)n + i], kind = meta >> 8;
+    const int32_t len = f.iplane(kPlLen)[i], rseq = f.iplane(kPlRseq)[i];
+    const uint32_t meta = f.plane(kPlMeta)[i], kind = meta >> 8, toff = f.plane(kPlToff)[i];
     if (tw[i] & kTEmpty) continue;
     if (lazy_zamboni && rseq != kNone && rseq <= h.min_seq) continue;
     if ((tw[i] & kTCont) && m > 0) {
       if (m - 1 < v->seg_cap && v->segs) v->segs[m - 1].len += (uint32_t)len;
-      const uint32_t toff = pl[5 * (size_t)n + i];
       for (int32_t u = 0; u < len; u++, nt++)
         if (nt < v->text_cap && v->text) v->text[nt] = c->h_arena[toff + (uint32_t)u];
       continue;
@@ -2184,18 +2167,17 @@ int mte_read_segments(mte_ctx* c, uint32_t doc, mte_seg_list* v) {
       mte_seg& s = v->segs[io];
       s.text_off = kind == 0 ? (uint32_t)nt : 0u;
       s.len = (uint32_t)len;
-      s.seq = (int32_t)pl[(size_t)n + i];
+      s.seq = f.iplane(kPlSeq)[i];
       s.removed_seq = rseq == kNone ? MTE_NOT_REMOVED : rseq;
-      s.removers = rseq == kNone ? 0u : pl[3 * (size_t)n + i];
+      s.removers = rseq == kNone ? 0u : f.plane(kPlRmask)[i];
       s.client = (int32_t)(meta & 0xffu) - 1;
       s.kind = kind;
       s.propset = MTE_NO_PROPS;
       if (v->props)
         for (uint32_t k = 0; k < c->n_keys; k++)
-          v->props[(size_t)io * c->n_keys + k] = pl[(size_t)(kFieldPlanes + k) * n + i];
+          v->props[(size_t)io * c->n_keys + k] = f.plane(kFieldPlanes + (int)k)[i];
     }
     if (kind == 0) {
-      const uint32_t toff = pl[5 * (size_t)n + i];
       for (int32_t u = 0; u < len; u++, nt++)
         if (nt < v->text_cap && v->text) v->text[nt] = c->h_arena[toff + (uint32_t)u];
     }

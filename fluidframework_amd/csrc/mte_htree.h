@@ -2349,6 +2349,9 @@ __global__ __launch_bounds__(64) MTE_HTREE_ATTR void htree_kernel(ReplayArgs a, 
   const bool ldoc = (hf & MTE_DOC_LOCAL_CLIENT) != 0;
   // its own documents from the start (a local client's, MTE_DOC_TREE, legacy
   // ones with delta events), the other legacy ones once TIER 2 hands them over
+  // This is doc_owner(hf) == kOwnHtree (mte_kernels.h) spelled out: through the
+  // function the compiler allocates this kernel's scalar registers otherwise
+  // (other SGPR spill counts).  A change of the routing rule changes this line.
   const bool own = ldoc || (hf & MTE_DOC_TREE) || ((hf & MTE_DOC_EVENTS) && !(hf & MTE_DOC_NEW_LENGTH_CALC));
   if (!own && !(hf & kHdrTreeHbm)) return;
   DocRun D;

@@ -41,6 +41,42 @@ constexpr uint32_t kHdrNeedsEsc = 0x80000000u;
 // the HBM-streamed pass (set per batch by the engine, mte_engine.hip)
 constexpr uint32_t kHdrRel = 0x08000000u;
 
+// ---- which pass replays a document -------------------------------------------
+// The routing rule, from the document's MTE_DOC_* flags (the kHdr* bits of a
+// header's flag word play no part).  The host's launch lists and checks
+// (mte_load_docs), reset_kernel and rel_route_kernel ask here; htree_kernel and
+// stream_kernel spell their `own` test out, for their register allocation, under
+// a comment that names this function.  A change of the rule is a change here
+// and at those two lines.
+enum DocOwner : uint32_t {
+  kOwnHtree,   // the HBM tree pass's own (mte_htree.h)
+  kOwnStream,  // the streamed flat pass's own (mte_stream.h): delta events, no local client
+  kOwnFlat,    // passes 1 - 3
+  kOwnFlatRs,  // passes 1 - 3, behind the per-batch round-sync check (round_sync_kernel)
+  kOwnTree,    // the register tree pass (mte_tree.h); the HBM tree pass takes it over past TIER 2
+};
+constexpr __host__ __device__ DocOwner doc_owner(uint32_t f) {
+  if ((f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) || ((f & MTE_DOC_EVENTS) && !(f & MTE_DOC_NEW_LENGTH_CALC)))
+    return kOwnHtree;
+  if (f & MTE_DOC_EVENTS) return kOwnStream;
+  if (f & MTE_DOC_NEW_LENGTH_CALC) return kOwnFlat;
+  if (f & MTE_DOC_ROUND_SYNC) return kOwnFlatRs;
+  return kOwnTree;
+}
+// the document carries the reference's tree words (the two tree owners)
+constexpr __host__ __device__ bool doc_has_tree(uint32_t f) {
+  return doc_owner(f) == kOwnHtree || doc_owner(f) == kOwnTree;
+}
+static_assert(doc_owner(MTE_DOC_NEW_LENGTH_CALC) == kOwnFlat, "plain new-calc");
+static_assert(doc_owner(0u) == kOwnTree, "plain legacy");
+static_assert(doc_owner(MTE_DOC_ROUND_SYNC) == kOwnFlatRs, "legacy with round-sync");
+static_assert(doc_owner(MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_EVENTS) == kOwnStream, "new-calc with events");
+static_assert(doc_owner(MTE_DOC_EVENTS) == kOwnHtree, "legacy with events");
+static_assert(doc_owner(MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_LOCAL_CLIENT) == kOwnHtree, "local client");
+static_assert(doc_owner(MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_TREE) == kOwnHtree, "MTE_DOC_TREE");
+static_assert(doc_owner(MTE_DOC_NEW_LENGTH_CALC | MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS | MTE_DOC_REFS) == kOwnHtree,
+              "local client with events and refs");
+
 // kStChunkCanon / kStChunkScan (chunk pass only): the canonical S_live of its
 // ops, and the chunk slots + summary entries those ops actually scanned
 enum StatIdx {

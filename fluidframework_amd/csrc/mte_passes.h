@@ -6,6 +6,8 @@
 // alone; mte_engine.hip drives them (launch_replay) and includes no kernel
 // header.  The pass headers include this one for the declarations below.  The
 // batched read-only queries (mte_query.h, mte_query.hip) follow the same rule.
+// Which pass replays a document is doc_owner() (mte_kernels.h), the one place
+// where the routing rule lives; nothing here restates it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -94,7 +96,12 @@ struct HtreeArgs {
   uint32_t maint;        // some document records maintenance (the htree_kernel<K, S, true> build)
 };
 
-template <int K> constexpr int kLocalPlanes = kFieldPlanes + 3 * K + 6;  // planes of a local-client / MTE_DOC_TREE document
+// planes of a local-client / MTE_DOC_TREE document (mte_htree.h names them); the
+// last is the removers of short ids 32 .. 63 (kRmHiPlane there).  As functions
+// of K for the host, which has it at run time.
+constexpr int local_planes(int K) { return kFieldPlanes + 3 * K + 6; }
+constexpr int rm_hi_plane(int K) { return local_planes(K) - 1; }
+template <int K> constexpr int kLocalPlanes = local_planes(K);
 
 // ---- local references (MTE_DOC_REFS, include/mte.h; mte_stream.h) -----------
 // A reference is kept as the text unit it sits on -- its arena offset (a

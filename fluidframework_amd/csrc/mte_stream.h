@@ -848,6 +848,12 @@ __global__ __launch_bounds__(256) void stream_kernel(ReplayArgs a) {
   // documents pass 2 escalated, and the new length-calc documents with delta
   // events and no local client (a local client's go to the HBM tree pass)
   const uint32_t hf = a.hdr[doc].flags;
+  // These two are doc_owner(hf) == kOwnHtree and == kOwnStream (mte_kernels.h)
+  // spelled out: through the function the compiler allocates this kernel's
+  // scalar registers otherwise (other SGPR spill counts).  The HBM tree pass's
+  // legacy documents with delta events pass the first test and leave at the
+  // third: nothing sets kHdrNeedsEsc on a document that pass 1 and
+  // rel_route_kernel do not own.  A change of the routing rule changes these.
   if (hf & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) return;  // the HBM tree pass's
   const bool own = (hf & (MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC)) == (MTE_DOC_EVENTS | MTE_DOC_NEW_LENGTH_CALC);
   if (!(hf & kHdrNeedsEsc) && !own) return;  // untouched doc: leave the header alone

@@ -516,7 +516,12 @@ int mte_create(const mte_config* cfg, mte_ctx** out);
 int mte_destroy(mte_ctx* ctx);
 const char* mte_last_error(const mte_ctx* ctx);
 
-/* Load (or reload) all documents; resets every doc to its initial state. */
+/* Load (or reload) all documents; resets every doc to its initial state.
+ * All or nothing: a load refused for its arguments (MTE_E_INVALID_ARG,
+ * MTE_E_UNSUPPORTED) leaves the previous load, its state included, as it was;
+ * one that fails after that (MTE_E_HIP: out of device memory, say) leaves the
+ * context without documents -- mte_submit and the read-outs then refuse any
+ * document count but 0 with MTE_E_INVALID_ARG -- until the next mte_load_docs. */
 int mte_load_docs(mte_ctx* ctx, uint32_t n_docs, const mte_doc_init* docs,
                   const uint16_t* text, uint64_t text_units,
                   const mte_propset* propsets, uint32_t n_propsets,

@@ -1,14 +1,17 @@
 """The life of one engine context (mte_engine.hip's host side): what survives a
-reload, which of the two batch slots a run replays and reads events from, and
+reload, what a refused load leaves, which of the two batch slots a run replays and reads events from, and
 the slot buffers and the text arena growing under a context in use.  Every
 case compares the context under test with a fresh context or with the
 specification (SpecOracle) on the same input, bit for bit."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from fluidframework_amd import gen
-from fluidframework_amd.abi import (DOC_EVENTS, DOC_TREE, F_MARKER, MTE_E_INVALID_ARG, NO_PROPS, OP_ANNOTATE,
-                                    OP_INSERT, MergeTreeError)
+from fluidframework_amd.abi import (DOC_EVENTS, DOC_INIT_DTYPE, DOC_NEW_LENGTH_CALC, DOC_TREE, F_MARKER, MTE_E_HIP,
+                                    MTE_E_INVALID_ARG, NO_PROPS, OP_ANNOTATE, OP_DTYPE, OP_INSERT, PROP_DTYPE,
+                                    PROPSET_DTYPE, MergeTreeError)
 from fluidframework_amd.engine import DeviceEngine
 from oracle import SpecOracle
 
@@ -91,6 +94,59 @@ def test_reload_leaves_nothing_of_the_earlier_load(fresh_outcomes, order):
         assert len(e.read_deltas(d)) == 0
     with pytest.raises(MergeTreeError):  # no batch of an earlier load is left to run
         e.run()
+
+
+def device_memory_bytes():
+    """Total memory of device 0, from the HIP runtime the engine loaded."""
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = C.CDLL(path)
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return total.value
+
+
+def test_refused_allocation_leaves_no_documents(fresh_outcomes):
+    """A load whose segment planes alone are at least twice the device's memory:
+    the driver refuses the request outright, mte_load_docs frees what it had
+    built and the context holds no documents -- no statuses, no batch taken --
+    until the next load, which computes what a fresh context does."""
+    s, ev, want = fresh_outcomes["plain"]
+    cap = 4096
+    e = DeviceEngine(s["n_keys"], seg_capacity=cap)
+    # six field planes and 4 or 8 property planes (one without keys), four bytes per segment slot
+    planes = 6 + (1 if s["n_keys"] == 0 else 4 if s["n_keys"] <= 4 else 8)
+    n = 2 * device_memory_bytes() // (cap * 4 * planes) + 1
+    inits = np.zeros(n, DOC_INIT_DTYPE)
+    inits["flags"] = DOC_NEW_LENGTH_CALC
+    inits["propset"] = NO_PROPS
+    with pytest.raises(MergeTreeError) as err:
+        e.load_docs(inits)
+    assert err.value.code == MTE_E_HIP
+    assert e.n_docs == n
+    with pytest.raises(MergeTreeError) as err:
+        e.statuses()
+    assert err.value.code == MTE_E_INVALID_ARG
+    with pytest.raises(MergeTreeError) as err:
+        e.submit({"op_offsets": np.zeros(n + 1, np.uint64), "ops": np.zeros(0, OP_DTYPE)})
+    assert err.value.code == MTE_E_INVALID_ARG
+    assert_outcome_equal(outcome(replay(e, s), ev), want)
+
+
+def test_load_refused_for_its_arguments_leaves_the_earlier_load(fresh_outcomes):
+    """A load propset no document references that runs past `props` is refused
+    before anything of the earlier load is touched: the statuses (a plain copy
+    of the headers, so asserted first) and then the digest are what they were."""
+    s, _, _ = fresh_outcomes["plain"]
+    e = replay(DeviceEngine(s["n_keys"]), s)
+    statuses, digest = e.statuses().copy(), e.digest().copy()
+    assert (s["inits"]["propset"] == NO_PROPS).all()
+    with pytest.raises(MergeTreeError) as err:
+        e.load_docs(s["inits"], s["init_text"], propsets=np.array([(1, 4)], PROPSET_DTYPE),
+                    props=np.zeros(2, PROP_DTYPE))
+    assert err.value.code == MTE_E_INVALID_ARG
+    np.testing.assert_array_equal(e.statuses(), statuses)
+    np.testing.assert_array_equal(e.digest(), digest)
 
 
 def test_pipelined_submits_read_the_events_of_the_slot_that_ran():
