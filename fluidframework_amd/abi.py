@@ -105,6 +105,37 @@ class MteTileQuery(C.Structure):
 class MteTileHit(C.Structure):
     _fields_ = [("pos", C.c_int32), ("status", C.c_int32), ("ref_type", C.c_uint32), ("reserved", C.c_uint32)]
 
+# mte_read_texts: a query and its answer
+TEXT_PLACEHOLDERS = 0x1
+TEXT_TO_END = 0x7fffffff
+TEXT_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("start", "<i4"), ("end", "<i4"), ("flags", "<u4")])
+assert TEXT_QUERY_DTYPE.itemsize == 16
+TEXT_INFO_DTYPE = np.dtype([("status", "<i4"), ("cur_seq", "<i4"), ("min_seq", "<i4"), ("length", "<u4"),
+                            ("n_units", "<u4"), ("reserved", "<u4"), ("offset", "<u8")])
+assert TEXT_INFO_DTYPE.itemsize == 32
+# mte_props_at
+POS_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4")])
+assert POS_QUERY_DTYPE.itemsize == 8
+POS_HIT_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("kind", "<u4"), ("reserved", "<u4")])
+assert POS_HIT_DTYPE.itemsize == 16
+
+
+class MteTextQuery(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("start", C.c_int32), ("end", C.c_int32), ("flags", C.c_uint32)]
+
+
+class MteTextInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("cur_seq", C.c_int32), ("min_seq", C.c_int32), ("length", C.c_uint32),
+                ("n_units", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64)]
+
+
+class MtePosQuery(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("pos", C.c_int32)]
+
+
+class MtePosHit(C.Structure):
+    _fields_ = [("status", C.c_int32), ("found", C.c_int32), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 class MteConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("n_keys", C.c_uint32),
@@ -150,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "mte_comm_unique_id", "mte_comm_init", "mte_comm_share", "mte_comm_barrier", "mte_comm_allreduce_f64",
     "mte_comm_gather_digests", "mte_comm_world", "mte_comm_destroy", "mte_read_deltas", "mte_set_event_capacity",
     "mte_set_ref_capacity", "mte_read_refs", "mte_read_refs_transient", "mte_read_ref_order", "mte_find_tiles",
+    "mte_read_texts", "mte_props_at",
 ]
 
 DOC_EVENTS = 0x8

@@ -714,7 +714,11 @@ struct mte_ctx {
   int world = 1, rank = 0;
   DevBuf<uint64_t> d_comm;  // digests of all ranks / scalar reductions (sized exactly, comm_staging)
   // mte_find_tiles: the call's queries + value ids, and its hits + property ids (words)
+  // (mte_props_at: its queries, and its hits + property ids)
   DevBuf<uint32_t> tile_in, tile_out;
+  // mte_read_texts: the queries (2 words each) then their offsets; the infos (4 words each); the units
+  DevBuf<uint64_t> text_in, text_info;
+  DevBuf<uint16_t> text_out;
   // per key, the largest property value id the context was given (load +
   // every batch) and whether any text segment or annotate ever carried it:
   // pass 1 packs the 4 property planes into one (kPack4) when every key's ids
@@ -1338,6 +1342,7 @@ int mte_destroy(mte_ctx* c) {
   if (c->h_rcount) (void)hipHostFree(c->h_rcount);
   free_buf(c->d_comm);
   free_buf(c->tile_in), free_buf(c->tile_out);
+  free_buf(c->text_in), free_buf(c->text_info), free_buf(c->text_out);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->tree_stream) (void)hipStreamDestroy(c->tree_stream);
@@ -2224,6 +2229,87 @@ int mte_find_tiles(mte_ctx* c, const mte_tile_query* q, uint32_t n, const uint32
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(out, res.data(), hw * 4);
   if (out_props && pw) std::memcpy(out_props, res.data() + hw, pw * 4);
+  return MTE_OK;
+}
+
+int mte_read_texts(mte_ctx* c, const mte_text_query* q, uint32_t n, mte_text_info* info, uint16_t* text,
+                   uint64_t text_cap, uint64_t* n_text) {
+  if (!c || !n_text || (n && (!q || !info))) return MTE_E_INVALID_ARG;
+  JOIN_TAIL(c);
+  *n_text = 0;
+  if (!n) return MTE_OK;
+  for (uint32_t i = 0; i < n; i++) {
+    const mte_text_query& t = q[i];
+    if (t.doc >= c->docs.n_docs || t.start < 0 || t.end < t.start || (t.flags & ~MTE_TEXT_PLACEHOLDERS))
+      return set_err(c, MTE_E_INVALID_ARG, "mte_read_texts: query %u (doc %u, [%d, %d), flags 0x%x)", i, t.doc, t.start,
+                     t.end, t.flags);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  static_assert(sizeof(mte_text_query) == 16 && sizeof(mte_text_info) == 32, "mte_read_texts packs these as 64-bit words");
+  // the queries up, the count, the infos down (the first wait) ...
+  if (int rc = grow(c, c->text_in, 3ull * n)) return rc;
+  if (int rc = grow(c, c->text_info, 4ull * n)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->text_in.p, q, 16ull * n, hipMemcpyHostToDevice, c->stream));
+  TextArgs a;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
+  a.cap = c->cap;
+  a.n = n;
+  a.q = (const mte_text_query*)c->text_in.p;
+  a.info = (mte_text_info*)c->text_info.p;
+  a.offset = c->text_in.p + 2ull * n;
+  a.arena = c->arena.p;
+  a.text = nullptr;
+  HIPCHK(c, launch_text_count(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, c->text_info.p, 32ull * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint64_t> off(n);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    off[i] = info[i].offset = total;
+    total += info[i].n_units;
+  }
+  *n_text = total;
+  if (!text || total > text_cap || !total) return MTE_OK;
+  // ... the offsets up, the gather, the units down (the second)
+  if (int rc = grow(c, c->text_out, total)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->text_in.p + 2ull * n, off.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));
+  a.text = c->text_out.p;
+  HIPCHK(c, launch_text_gather(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(text, c->text_out.p, total * 2, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MTE_OK;
+}
+
+int mte_props_at(mte_ctx* c, const mte_pos_query* q, uint32_t n, mte_pos_hit* out, uint32_t* out_props) {
+  if (!c || (n && (!q || !out))) return MTE_E_INVALID_ARG;
+  JOIN_TAIL(c);
+  if (!n) return MTE_OK;
+  for (uint32_t i = 0; i < n; i++)
+    if (q[i].doc >= c->docs.n_docs || q[i].pos < 0)
+      return set_err(c, MTE_E_INVALID_ARG, "mte_props_at: query %u (doc %u, pos %d)", i, q[i].doc, q[i].pos);
+  HIPCHK(c, hipSetDevice(c->device));
+  // one upload, one launch, one download (hits, then the property ids)
+  static_assert(sizeof(mte_pos_query) == 8 && sizeof(mte_pos_hit) == 16, "mte_props_at packs these as words");
+  const uint64_t qw = 2ull * n, hw = 4ull * n, pw = out_props ? (uint64_t)n * c->n_keys : 0;
+  std::vector<uint32_t> res(hw + pw);
+  if (int rc = grow(c, c->tile_in, qw)) return rc;
+  if (int rc = grow(c, c->tile_out, res.size())) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->tile_in.p, q, qw * 4, hipMemcpyHostToDevice, c->stream));
+  PosArgs a;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
+  a.cap = c->cap;
+  a.n_keys = c->n_keys;
+  a.n = n;
+  a.q = (const mte_pos_query*)c->tile_in.p;
+  a.out = (mte_pos_hit*)c->tile_out.p;
+  a.out_props = pw ? c->tile_out.p + hw : nullptr;
+  HIPCHK(c, launch_props_at(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res.data(), c->tile_out.p, res.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(out, res.data(), hw * 4);
+  if (pw) std::memcpy(out_props, res.data() + hw, pw * 4);
   return MTE_OK;
 }
 

@@ -209,4 +209,32 @@ struct TileArgs {
 };
 hipError_t launch_find_tiles(const TileArgs& a, hipStream_t s);
 
+// mte_read_texts: text_count_kernel fills info (all but offset), the host sums
+// the counts into offsets, text_gather_kernel copies the units
+struct TextArgs {
+  const DocHdr* hdr;
+  SegSoA soa;
+  uint32_t cap;
+  uint32_t n;                  // queries; one wave each
+  const mte_text_query* q;     // validated by the host (doc, start, end, flags)
+  mte_text_info* info;         // [n] (count)
+  const uint64_t* offset;      // [n] where each query's units start in text (gather)
+  const uint16_t* arena;       // (gather)
+  uint16_t* text;              // (gather)
+};
+hipError_t launch_text_count(const TextArgs& a, hipStream_t s);
+hipError_t launch_text_gather(const TextArgs& a, hipStream_t s);
+
+struct PosArgs {
+  const DocHdr* hdr;
+  SegSoA soa;
+  uint32_t cap;
+  uint32_t n_keys;
+  uint32_t n;                  // queries; one wave each
+  const mte_pos_query* q;      // validated by the host (doc, pos)
+  mte_pos_hit* out;            // [n]
+  uint32_t* out_props;         // [n][n_keys], or null
+};
+hipError_t launch_props_at(const PosArgs& a, hipStream_t s);
+
 }  // namespace mte

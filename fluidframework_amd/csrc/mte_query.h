@@ -24,6 +24,25 @@
 // only; the one write is the query's own answer.  A document of a million
 // segments is 16k steps of one wave: correct, slow; a tile-parallel variant
 // (as dg_*_kernel is of the digest) is not built.
+//
+// text_count_kernel and text_gather_kernel answer mte_read_texts:
+// MergeTreeTextHelper.getText (MergeTreeTextHelper.ts:20-74) stated flat, the
+// units at own-view positions start <= p < min(end, length), a visible marker
+// position contributing nothing or one 0x0020 (MTE_TEXT_PLACEHOLDERS).  The
+// count walks the whole document (it also gives getLength) over rseq, len and
+// meta; the host turns the counts into offsets; the gather runs the same walk
+// up to `end` and copies unit-parallel: per 64-slot step each lane's clipped
+// contribution is scanned, (exclusive sum, source) staged in the wave's own
+// 512 B of LDS, and lane j of each round of 64 output units finds its slot by a
+// 6-step search and copies one unit, so consecutive lanes write consecutive
+// units whether the step is one segment of thousands of units or 64 segments
+// of one.  props_at_kernel answers mte_props_at (Client.getPropertiesAtPosition,
+// client.ts:1133-1141): the visible segment with P <= pos < P + L.  All three
+// have find_tiles_kernel's shape (one wave per query, four per workgroup), and
+// like it serve big contexts over the flat planes with one wave per document:
+// correct, slow for a document of a million segments; no tile-parallel variant
+// is built.  The four waves of a workgroup walk different documents: nothing
+// block-wide sits in any loop.
 #pragma once
 
 #include "mte_kernels.h"
@@ -83,6 +102,155 @@ __global__ __launch_bounds__(256) void find_tiles_kernel(TileArgs a) {
     h.pos = hit_pos;
     h.status = status;
     h.ref_type = hit_slot >= 0 ? hit_kind - 1 : 0u;
+    h.reserved = 0;
+    a.out[qi] = h;
+  }
+  if (a.out_props && (uint32_t)l < a.n_keys)
+    a.out_props[(uint64_t)qi * a.n_keys + l] =
+        hit_slot >= 0 ? a.soa.props[(uint64_t)l * a.soa.plane_stride + db + hit_slot] : 0u;
+}
+
+// what slot [P, P + L) of kind `kind` gives a query [start, end): its clipped
+// span's first position and its units (a marker's only with placeholders)
+__device__ __forceinline__ int32_t text_clip(int32_t P, int32_t L, uint32_t kind, int32_t start, int32_t end,
+                                             bool placeholders, int32_t* lo) {
+  *lo = P > start ? P : start;
+  const int32_t hi = P + L < end ? P + L : end;
+  return (hi > *lo && (kind == 0 || placeholders)) ? hi - *lo : 0;
+}
+
+__global__ __launch_bounds__(256) void text_count_kernel(TextArgs a) {
+  const int w = threadIdx.x / kWave;
+  const int l = lane_id();
+  const uint32_t qi = blockIdx.x * kQueriesPerBlock + (uint32_t)w;
+  if (qi >= a.n) return;
+  const mte_text_query q = a.q[qi];
+  const uint32_t doc = uni(q.doc);
+  const int32_t start = uni(q.start), end = uni(q.end);
+  const bool ph = (uni(q.flags) & MTE_TEXT_PLACEHOLDERS) != 0;
+  const DocHdr h = a.hdr[doc];
+  int n = h.status == MTE_OK ? h.nseg : 0;  // a stopped document answers length = n_units = 0
+  n = n < 0 ? 0 : (n > (int)a.cap ? (int)a.cap : n);
+  const uint64_t db = (uint64_t)doc * a.cap;
+
+  int32_t carry = 0, mine = 0;
+  for (int c0 = 0; c0 < n; c0 += kWave) {
+    const int i = c0 + l;
+    const bool vis = i < n && a.soa.rseq[db + i] == kNone;
+    const int32_t L = vis ? a.soa.len[db + i] : 0;
+    const uint32_t kind = vis ? a.soa.meta[db + i] >> 8 : 0u;
+    const int32_t incl = wave_incl_scan(L);
+    int32_t lo;
+    mine += text_clip(carry + incl - L, L, kind, start, end, ph, &lo);
+    carry += rdlane(incl, kWave - 1);
+  }
+  const int32_t units = rdlane(wave_incl_scan(mine), kWave - 1);
+  if (l == 0) {
+    mte_text_info* o = a.info + qi;  // offset is the host's
+    o->status = h.status;
+    o->cur_seq = h.cur_seq;
+    o->min_seq = h.min_seq;
+    o->length = (uint32_t)carry;
+    o->n_units = (uint32_t)units;
+    o->reserved = 0;
+  }
+}
+
+// the wave's LDS writes before, its reads after (no other wave shares the slice)
+__device__ __forceinline__ void query_fence_wave() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+constexpr uint32_t kTextMarker = 0x80000000u;  // staged exclusive sum: the slot is a marker
+
+__global__ __launch_bounds__(256) void text_gather_kernel(TextArgs a) {
+  __shared__ uint2 stage[kQueriesPerBlock][kWave];  // (exclusive sum | kTextMarker, arena offset)
+  const int w = threadIdx.x / kWave;
+  const int l = lane_id();
+  const uint32_t qi = blockIdx.x * kQueriesPerBlock + (uint32_t)w;
+  if (qi >= a.n) return;
+  const mte_text_query q = a.q[qi];
+  const uint32_t doc = uni(q.doc);
+  const int32_t start = uni(q.start), end = uni(q.end);
+  const bool ph = (uni(q.flags) & MTE_TEXT_PLACEHOLDERS) != 0;
+  int n = a.hdr[doc].status == MTE_OK ? a.hdr[doc].nseg : 0;
+  n = n < 0 ? 0 : (n > (int)a.cap ? (int)a.cap : n);
+  const uint64_t db = (uint64_t)doc * a.cap;
+  uint16_t* out = a.text + uni64(a.offset[qi]);
+  uint2* st = stage[w];
+
+  int32_t carry = 0;
+  for (int c0 = 0; c0 < n; c0 += kWave) {
+    if (carry >= end) break;  // the step starts at or beyond end
+    const int i = c0 + l;
+    const bool vis = i < n && a.soa.rseq[db + i] == kNone;
+    const int32_t L = vis ? a.soa.len[db + i] : 0;
+    const uint32_t kind = vis ? a.soa.meta[db + i] >> 8 : 0u;
+    const int32_t incl = wave_incl_scan(L);
+    const int32_t P = carry + incl - L;
+    int32_t lo;
+    const int32_t c = text_clip(P, L, kind, start, end, ph, &lo);
+    const int32_t cincl = wave_incl_scan(c);
+    const int32_t T = rdlane(cincl, kWave - 1);  // units this step gives: below 2^31, as length is
+    if (T > 0) {
+      const uint32_t src = (c > 0 && kind == 0) ? a.soa.toff[db + i] + (uint32_t)(lo - P) : 0u;
+      st[l] = make_uint2((uint32_t)(cincl - c) | (kind != 0 ? kTextMarker : 0u), src);
+      query_fence_wave();
+      for (int32_t j = l; j < T; j += kWave) {
+        // the last slot whose exclusive sum is <= j: slots that give nothing
+        // share theirs with the next giving one, so this is the giving one
+        int s = 0;
+#pragma unroll
+        for (int b = kWave / 2; b > 0; b >>= 1)
+          if ((int32_t)(st[s + b].x & ~kTextMarker) <= j) s += b;
+        const uint2 e = st[s];
+        out[j] = (e.x & kTextMarker) ? (uint16_t)0x0020 : a.arena[e.y + (uint32_t)(j - (int32_t)(e.x & ~kTextMarker))];
+      }
+      query_fence_wave();  // the next step overwrites the slice
+      out += T;
+    }
+    carry += rdlane(incl, kWave - 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void props_at_kernel(PosArgs a) {
+  const int w = threadIdx.x / kWave;
+  const int l = lane_id();
+  const uint32_t qi = blockIdx.x * kQueriesPerBlock + (uint32_t)w;
+  if (qi >= a.n) return;
+  const mte_pos_query q = a.q[qi];
+  const uint32_t doc = uni(q.doc);
+  const int32_t pos = uni(q.pos);
+  const int32_t status = a.hdr[doc].status;
+  int n = status == MTE_OK ? a.hdr[doc].nseg : 0;
+  n = n < 0 ? 0 : (n > (int)a.cap ? (int)a.cap : n);
+  const uint64_t db = (uint64_t)doc * a.cap;
+
+  int32_t hit_slot = -1, carry = 0;
+  uint32_t hit_kind = 0;
+  for (int c0 = 0; c0 < n; c0 += kWave) {
+    if (carry > pos) break;
+    const int i = c0 + l;
+    const bool vis = i < n && a.soa.rseq[db + i] == kNone;
+    const int32_t L = vis ? a.soa.len[db + i] : 0;
+    const uint32_t kind = vis ? a.soa.meta[db + i] >> 8 : 0u;
+    const int32_t incl = wave_incl_scan(L);
+    const int32_t P = carry + incl - L;
+    const unsigned long long b = __ballot(L > 0 && P <= pos && pos < P + L);
+    if (b) {
+      const int s = __builtin_ctzll(b);
+      hit_kind = rdlane(kind, s);
+      hit_slot = c0 + s;
+      break;
+    }
+    carry += rdlane(incl, kWave - 1);
+  }
+  if (l == 0) {
+    mte_pos_hit h;
+    h.status = status;
+    h.found = hit_slot >= 0;
+    h.kind = hit_kind;
     h.reserved = 0;
     a.out[qi] = h;
   }

@@ -3,9 +3,27 @@
 
 namespace mte {
 
+namespace {
+inline uint32_t query_blocks(uint32_t n) { return (n + kQueriesPerBlock - 1) / kQueriesPerBlock; }
+}  // namespace
+
 hipError_t launch_find_tiles(const TileArgs& a, hipStream_t s) {
-  const uint32_t blocks = (a.n + kQueriesPerBlock - 1) / kQueriesPerBlock;
-  hipLaunchKernelGGL(find_tiles_kernel, dim3(blocks), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  hipLaunchKernelGGL(find_tiles_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_text_count(const TextArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(text_count_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_text_gather(const TextArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(text_gather_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_props_at(const PosArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(props_at_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
   return hipGetLastError();
 }
 

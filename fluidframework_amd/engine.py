@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _native
 from .abi import (DELTA_DTYPE, DOC_INIT_DTYPE, EXPORTED_SYMBOLS, OP_DTYPE, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE,
+                  POS_HIT_DTYPE, POS_QUERY_DTYPE, TEXT_INFO_DTYPE, TEXT_PLACEHOLDERS, TEXT_QUERY_DTYPE, TEXT_TO_END,
                   TILE_HIT_DTYPE, TILE_PRECEDING, TILE_QUERY_DTYPE,
                   MergeTreeError, MteBatch, MteConfig, MteDocView, MteSegList, MteStats, ptr)
 from .packing import units_to_str
@@ -274,6 +275,74 @@ class DeviceEngine(EngineBase):
                 raise MergeTreeError(int(h["status"]), f"find_tiles: document {int(q[i]['doc'])}")
             out.append(None if h["pos"] < 0 else
                        {"pos": int(h["pos"]), "refType": int(h["ref_type"]), "props": interner.decode_props(props[i])})
+        return out
+
+    def read_texts_raw(self, q, fill=True):
+        """mte_read_texts over TEXT_QUERY_DTYPE[n] -> (TEXT_INFO_DTYPE[n], uint16
+        units): every query's text, at info["offset"] .. + info["n_units"], from
+        one device call (two when the engine's host buffer has to grow first);
+        fill=False asks for the sizes only and returns no units."""
+        q = _arr(q, TEXT_QUERY_DTYPE)
+        info = np.zeros(len(q), TEXT_INFO_DTYPE)
+        n = C.c_uint64()
+        if not fill:
+            self._check(self.lib.mte_read_texts(self.ctx, ptr(q), len(q), ptr(info), None, 0, C.byref(n)),
+                        "read_texts")
+            return info, np.zeros(0, np.uint16)
+        buf = getattr(self, "_text_buf", None)
+        if buf is None:
+            buf = self._text_buf = np.zeros(1 << 16, np.uint16)
+        self._check(self.lib.mte_read_texts(self.ctx, ptr(q), len(q), ptr(info), ptr(buf), len(buf), C.byref(n)),
+                    "read_texts")
+        if n.value > len(buf):  # size-then-fill: nothing was written
+            buf = self._text_buf = np.zeros(2 * n.value, np.uint16)
+            self._check(self.lib.mte_read_texts(self.ctx, ptr(q), len(q), ptr(info), ptr(buf), len(buf), C.byref(n)),
+                        "read_texts")
+        return info, buf[: n.value].copy()
+
+    def read_texts(self, queries):
+        """getText for many documents at once (include/mte.h mte_read_texts):
+        a query is `doc` or (doc, start, end[, placeholders]) -- end None or
+        TEXT_TO_END for the document's length, placeholders: one space per
+        visible marker position -> [str], one batched read-out for all of them.
+        Raises MergeTreeError for a document whose status is not OK."""
+        q = np.zeros(len(queries), TEXT_QUERY_DTYPE)
+        for i, t in enumerate(queries):
+            t = (t,) if isinstance(t, (int, np.integer)) else tuple(t)
+            end = t[2] if len(t) > 2 and t[2] is not None else TEXT_TO_END
+            q[i] = (t[0], t[1] if len(t) > 1 else 0, end, TEXT_PLACEHOLDERS if len(t) > 3 and t[3] else 0)
+        info, text = self.read_texts_raw(q)
+        out = []
+        for i, h in enumerate(info):
+            if h["status"] != 0:
+                raise MergeTreeError(int(h["status"]), f"read_texts: document {int(q[i]['doc'])}")
+            o = int(h["offset"])
+            out.append(units_to_str(text[o: o + int(h["n_units"])]))
+        return out
+
+    def props_at_raw(self, q, want_props=True):
+        """mte_props_at over POS_QUERY_DTYPE[n] -> (POS_HIT_DTYPE[n], uint32[n,
+        n_keys] or None): every query answered by one device call."""
+        q = _arr(q, POS_QUERY_DTYPE)
+        hits = np.zeros(len(q), POS_HIT_DTYPE)
+        props = np.zeros((len(q), self.n_keys), np.uint32) if want_props else None
+        self._check(self.lib.mte_props_at(self.ctx, ptr(q), len(q), ptr(hits), ptr(props)), "props_at")
+        return hits, props
+
+    def props_at(self, queries, interner):
+        """Client.getPropertiesAtPosition for many documents at once (include/mte.h
+        mte_props_at): queries = [(doc, pos)] -> [props | None] (the segment's
+        properties, {} when it has none; None: pos at or past the length), one
+        device call for all of them.  Raises MergeTreeError for a document whose status is not OK."""
+        q = np.zeros(len(queries), POS_QUERY_DTYPE)
+        for i, (doc, pos) in enumerate(queries):
+            q[i] = (doc, pos)
+        hits, props = self.props_at_raw(q)
+        out = []
+        for i, h in enumerate(hits):
+            if h["status"] != 0:
+                raise MergeTreeError(int(h["status"]), f"props_at: document {int(q[i]['doc'])}")
+            out.append(interner.decode_props(props[i]) if h["found"] else None)
         return out
 
     def _read_doc(self, doc, vptr):

@@ -161,6 +161,20 @@ export interface TileResult {
   pos: number;
 }
 
+export interface TextQuery {
+  client: BatchClient;
+  /** default 0; a negative start counts as 0 */
+  start?: number;
+  /** default: the client's length */
+  end?: number;
+  /** one space per visible marker position (getTextWithPlaceholders); default false */
+  placeholders?: boolean;
+}
+export interface PositionQuery {
+  client: BatchClient;
+  pos: number;
+}
+
 export class MergeTreeEngine {
   constructor(options?: EngineOptions);
   readonly nKeys: number;
@@ -175,6 +189,14 @@ export class MergeTreeEngine {
   /** SharedString.findTile for many documents: one flush, one sync and one
    *  device call (mte_find_tiles) for the whole array, any document order. */
   findTiles(queries: TileQuery[]): (TileResult | undefined)[];
+  /** getText(start?, end?) for many documents: one flush, one sync and one
+   *  device call (mte_read_texts) for the whole array, any document order,
+   *  repeats allowed; one string per query. */
+  getTexts(queries: TextQuery[]): string[];
+  /** getPropertiesAtPosition for many documents: one flush, one sync and one
+   *  device call (mte_props_at) for the whole array; undefined where the
+   *  segment has no properties or pos is at or past the length. */
+  getPropertiesAt(queries: PositionQuery[]): (PropertySet | undefined)[];
   digests(): BigUint64Array;
   statuses(): Int32Array;
   stats(): EngineStats;

@@ -362,6 +362,81 @@ class MergeTreeEngine {
     return out;
   }
 
+  /** The queries' clients checked (a BatchClient of this engine), as findTiles does. */
+  _queryDoc(what, i, t) {
+    if (!t || !(t.client instanceof BatchClient) || t.client.engine !== this) {
+      throw new MergeTreeError(-1, what + ": query " + i + " is not for a client of this engine");
+    }
+    return t.client.doc;
+  }
+
+  /** getText for many documents at once (mte_read_texts): one flush, one sync
+   *  and one device call for the whole array, in any document order, with
+   *  repeats.  A query is {client, start?, end?, placeholders?}: the units at
+   *  start <= p < min(end, length) of the client's own view (a negative start
+   *  counts as 0, as gatherText's does), markers giving nothing or, with
+   *  placeholders, one space each (getTextWithPlaceholders).  -> one string
+   *  per query.  Throws for a document whose status is not OK.  One wavefront
+   *  walks each queried document: slow over a document of a million segments.
+   *  @param {{client: BatchClient, start?: number, end?: number, placeholders?: boolean}[]} queries */
+  getTexts(queries) {
+    this.flush();
+    this.sync();
+    const n = queries.length;
+    const q = new Uint32Array(4 * n);
+    for (let i = 0; i < n; i++) {
+      const t = queries[i];
+      const doc = this._queryDoc("getTexts", i, t);
+      let start = t.start === undefined ? 0 : t.start;
+      let end = t.end === undefined ? 0x7fffffff : t.end;
+      if (!Number.isInteger(start) || !Number.isInteger(end)) {
+        throw new MergeTreeError(-1, "getTexts: query " + i + ": [" + start + ", " + end + ")");
+      }
+      start = Math.min(Math.max(start, 0), 0x7fffffff);
+      end = Math.min(Math.max(end, start), 0x7fffffff);  // end < start reads nothing
+      q.set([doc, start, end, t.placeholders ? 1 : 0], 4 * i);
+    }
+    if (n === 0) return [];
+    const r = this.addon.readTexts(this.ctx, q);
+    const out = new Array(n);
+    for (let i = 0; i < n; i++) {
+      const status = r.info[8 * i] | 0;
+      if (status !== 0) throw docError(status, queries[i].client.doc);
+      const off = r.info[8 * i + 6] + r.info[8 * i + 7] * 4294967296;
+      out[i] = unitsToString(r.text.subarray(off, off + r.info[8 * i + 4]));
+    }
+    return out;
+  }
+
+  /** Client.getPropertiesAtPosition for many documents at once (mte_props_at):
+   *  one flush, one sync and one device call for the whole array.  -> per
+   *  query the properties of the visible segment holding pos in the client's
+   *  own view; undefined when it has none, or pos is negative or at or past the
+   *  length.  Throws for a document whose status is not OK.
+   *  @param {{client: BatchClient, pos: number}[]} queries */
+  getPropertiesAt(queries) {
+    this.flush();
+    this.sync();
+    const n = queries.length;
+    const q = new Uint32Array(2 * n), outside = new Array(n).fill(false);
+    for (let i = 0; i < n; i++) {
+      const t = queries[i];
+      const doc = this._queryDoc("getPropertiesAt", i, t);
+      if (!Number.isInteger(t.pos)) throw new MergeTreeError(-1, "getPropertiesAt: query " + i + ": pos " + t.pos);
+      outside[i] = t.pos < 0 || t.pos > 0x7fffffff;  // no segment holds it
+      q.set([doc, outside[i] ? 0x7fffffff : t.pos], 2 * i);
+    }
+    const out = new Array(n).fill(undefined);  // no holes: forEach / map visit every answer
+    if (n === 0) return out;
+    const r = this.addon.propsAt(this.ctx, q, this.nKeys);
+    for (let i = 0; i < n; i++) {
+      if (r.hits[4 * i] !== 0) throw docError(r.hits[4 * i], queries[i].client.doc);
+      if (r.hits[4 * i + 1] === 0 || outside[i]) continue;
+      out[i] = this.interner.decode(r.props.subarray(i * this.nKeys, (i + 1) * this.nKeys));
+    }
+    return out;
+  }
+
   /** Per-doc canonical digests (4 x u64 each, DESIGN.md "Digest"). */
   digests() {
     this.flush();

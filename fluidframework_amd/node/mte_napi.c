@@ -55,6 +55,8 @@ static int throw_rc(napi_env env, int rc, mte_ctx* ctx, const char* what) {
 typedef struct {
   mte_ctx* ctx;
   uint32_t n_keys; /* the context's property planes: the read-outs size their buffers by it */
+  uint16_t* text;  /* readTexts: where mte_read_texts fills, kept from call to call */
+  uint64_t text_cap;
 } ctx_box;
 
 static void ctx_finalize(napi_env env, void* data, void* hint) {
@@ -62,6 +64,7 @@ static void ctx_finalize(napi_env env, void* data, void* hint) {
   (void)hint;
   ctx_box* b = (ctx_box*)data;
   if (b->ctx) mte_destroy(b->ctx);
+  free(b->text);
   free(b);
 }
 
@@ -699,6 +702,103 @@ static napi_value js_find_tiles(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* readTexts(ctx, queries) -> {info Uint32Array(8n) (mte_text_info: status,
+   curSeq, minSeq, length, nUnits, 0, offset low, offset high), text
+   Uint16Array(n_text)}: mte_read_texts over queries = Uint32Array(4n)
+   (mte_text_query: doc, start, end, flags), one call (a second only when the
+   context's fill buffer has to grow first).  Weak, as mte_find_tiles is. */
+extern __typeof__(mte_read_texts) mte_read_texts __attribute__((weak));
+extern __typeof__(mte_props_at) mte_props_at __attribute__((weak));
+
+static napi_value js_read_texts(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return NULL;
+  ctx_box* box = get_box(env, argv[0]);
+  if (!box) return NULL;
+  void* q = NULL;
+  size_t qb = 0;
+  if (!get_bytes(env, argv[1], &q, &qb)) return NULL;
+  if (!mte_read_texts) {
+    throw_rc(env, MTE_E_UNSUPPORTED, NULL, "readTexts: this engine library has no mte_read_texts");
+    return NULL;
+  }
+  if (qb % sizeof(mte_text_query) || qb / sizeof(mte_text_query) > 0xffffffffu) {
+    throw_rc(env, MTE_E_INVALID_ARG, box->ctx, "readTexts: buffer size");
+    return NULL;
+  }
+  const size_t n = qb / sizeof(mte_text_query);
+  napi_value o, ab_i, ab_t, ti, tt;
+  void *pi = NULL, *pt = NULL;
+  uint64_t nt = 0;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(mte_text_info), &pi, &ab_i));
+  for (int pass = 0; pass < 2; pass++) {
+    if (throw_rc(env, mte_read_texts(box->ctx, (const mte_text_query*)q, (uint32_t)n, (mte_text_info*)pi, box->text,
+                                     box->text_cap, &nt),
+                 box->ctx, "mte_read_texts"))
+      return NULL;
+    if (nt <= box->text_cap) break;
+    if (pass == 1) { /* the documents cannot change between the two calls */
+      throw_rc(env, MTE_E_STATE, box->ctx, "readTexts: the text grew between the size and the fill");
+      return NULL;
+    }
+    free(box->text);
+    box->text_cap = 0;
+    box->text = (uint16_t*)malloc((size_t)nt * 4);
+    if (!box->text) {
+      throw_rc(env, MTE_E_OOM, box->ctx, "readTexts");
+      return NULL;
+    }
+    box->text_cap = nt * 2;
+  }
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)nt * 2, &pt, &ab_t));
+  if (nt) memcpy(pt, box->text, (size_t)nt * 2);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n * 8, ab_i, 0, &ti));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint16_array, (size_t)nt, ab_t, 0, &tt));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "info", ti);
+  napi_set_named_property(env, o, "text", tt);
+  return o;
+}
+
+/* propsAt(ctx, queries, nKeys) -> {hits Int32Array(4n) (mte_pos_hit: status,
+   found, kind, 0), props Uint32Array(n * nKeys)}: mte_props_at over queries =
+   Uint32Array(2n) (mte_pos_query: doc, pos). */
+static napi_value js_props_at(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return NULL;
+  ctx_box* box = get_box(env, argv[0]);
+  if (!box) return NULL;
+  void* q = NULL;
+  size_t qb = 0;
+  uint32_t nk = 0;
+  if (!get_bytes(env, argv[1], &q, &qb)) return NULL;
+  NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &nk));
+  if (!check_nkeys(env, box, nk)) return NULL;
+  if (!mte_props_at) {
+    throw_rc(env, MTE_E_UNSUPPORTED, NULL, "propsAt: this engine library has no mte_props_at");
+    return NULL;
+  }
+  if (qb % sizeof(mte_pos_query) || qb / sizeof(mte_pos_query) > 0xffffffffu) {
+    throw_rc(env, MTE_E_INVALID_ARG, box->ctx, "propsAt: buffer size");
+    return NULL;
+  }
+  const size_t n = qb / sizeof(mte_pos_query);
+  napi_value o, ab_h, ab_p, th, tp;
+  void *ph = NULL, *pp = NULL;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(mte_pos_hit), &ph, &ab_h));
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * nk * 4, &pp, &ab_p));
+  if (throw_rc(env, mte_props_at(box->ctx, (const mte_pos_query*)q, (uint32_t)n, (mte_pos_hit*)ph,
+                                 n && nk ? (uint32_t*)pp : NULL),
+               box->ctx, "mte_props_at"))
+    return NULL;
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n * 4, ab_h, 0, &th));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n * nk, ab_p, 0, &tp));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "hits", th);
+  napi_set_named_property(env, o, "props", tp);
+  return o;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   const napi_property_descriptor d[] = {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -732,6 +832,8 @@ static napi_value init(napi_env env, napi_value exports) {
       /* not enumerable: Object.keys() of the addon stays the list of functions
          every engine library serves; findTiles depends on the library (above) */
       {"findTiles", NULL, js_find_tiles, NULL, NULL, NULL, napi_default, NULL},
+      {"readTexts", NULL, js_read_texts, NULL, NULL, NULL, napi_default, NULL},
+      {"propsAt", NULL, js_props_at, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

@@ -665,6 +665,66 @@ typedef struct mte_tile_hit {
 int mte_find_tiles(mte_ctx* ctx, const mte_tile_query* q, uint32_t n, const uint32_t* values, uint32_t n_values,
                    mte_tile_hit* out, uint32_t* out_props);
 
+/* ---- Batched text read-out: getText for many documents ---------------------
+ * Each query asks one document for the units at positions p of its own view
+ * with start <= p < min(end, length) -- MergeTreeTextHelper.getText
+ * (MergeTreeTextHelper.ts:20-74) stated flat.  A text unit gives itself; a
+ * visible marker position gives nothing, or one 0x0020 unit with
+ * MTE_TEXT_PLACEHOLDERS (placeholder.repeat(cachedLength) for " "; the "*"
+ * placeholder is not served).  Visible as in mte_find_tiles and mte_read_doc:
+ * a local client's pending inserts count, its pending removals do not.
+ *
+ * info[i] holds the document's status and collab window, its getLength()
+ * (every visible unit, markers included), the units the query gave and where
+ * they start in `text`: offsets are the exclusive prefix sums of n_units in
+ * query order, so info[n-1].offset + info[n-1].n_units == *n_text.  Queries may
+ * name documents in any order, with repeats; n == 0 launches nothing.  A
+ * document whose status is not MTE_OK answers length = n_units = 0 with its
+ * status.
+ *
+ * Size-then-fill: info and *n_text are always produced; `text` is written only
+ * when it is non-NULL and *n_text <= text_cap, and left untouched otherwise
+ * (the call still returns MTE_OK: compare *n_text and call again).  The device
+ * work is one upload of the queries, a count kernel, one download of info and,
+ * when filling, an upload of the offsets, a gather kernel and one download of
+ * the text: two synchronisations, whatever n and the number of documents.
+ * MTE_E_INVALID_ARG, before any launch, for a null context or n_text,
+ * doc >= n_docs, start < 0, end < start or an unknown flag.  One wavefront walks a whole
+ * document per query (no tile-parallel variant exists yet).                  */
+#define MTE_TEXT_PLACEHOLDERS 0x1u      /* one 0x0020 unit per visible marker position */
+#define MTE_TEXT_TO_END       0x7fffffff
+typedef struct mte_text_query {
+  uint32_t doc;
+  int32_t  start;   /* >= 0 */
+  int32_t  end;     /* >= start; MTE_TEXT_TO_END = getLength() */
+  uint32_t flags;   /* MTE_TEXT_PLACEHOLDERS or 0 */
+} mte_text_query;   /* 16 B */
+typedef struct mte_text_info {
+  int32_t  status, cur_seq, min_seq;
+  uint32_t length;    /* getLength(): all visible units, markers included */
+  uint32_t n_units;   /* units this query wrote */
+  uint32_t reserved;
+  uint64_t offset;    /* where they start in `text` */
+} mte_text_info;      /* 32 B */
+int mte_read_texts(mte_ctx* ctx, const mte_text_query* q, uint32_t n, mte_text_info* info,
+                   uint16_t* text, uint64_t text_cap, uint64_t* n_text);
+
+/* ---- Batched point query: getPropertiesAtPosition for many documents -------
+ * Client.getPropertiesAtPosition (client.ts:1133-1141) through
+ * getContainingSegment: per query the visible segment of the document's own
+ * view with P <= pos < P + L.  found is 0 or 1 (0 at and past getLength());
+ * kind is the segment's kind, 0 for text and 1 + refType for a marker;
+ * out_props, when given, receives the segment's n_keys value ids per query
+ * (zeros where nothing is found).  No segment position or length is returned:
+ * those depend on the segmentation.  One upload, one launch, one download for
+ * all n queries, any document order, repeats allowed; n == 0 launches nothing;
+ * a document whose status is not MTE_OK answers found = 0 with its status.
+ * MTE_E_INVALID_ARG, before any launch, for a null context, doc >= n_docs or
+ * pos < 0.                                                                   */
+typedef struct mte_pos_query { uint32_t doc; int32_t pos; } mte_pos_query;
+typedef struct mte_pos_hit   { int32_t status; int32_t found; uint32_t kind; uint32_t reserved; } mte_pos_hit;
+int mte_props_at(mte_ctx* ctx, const mte_pos_query* q, uint32_t n, mte_pos_hit* out, uint32_t* out_props);
+
 int mte_doc_status(mte_ctx* ctx, int32_t* out, uint32_t n_docs);
 int mte_stats_get(mte_ctx* ctx, mte_stats* out);
 /* Statistics accounting (the counters of mte_stats, like the reference's
