@@ -672,11 +672,19 @@ __device__ __forceinline__ void burst_run(DocRun& D, const ReplayArgs& a, uint32
   uint32_t st[kNumStats] = {};
   if constexpr (E <= kStepVEmax) {
     // pass 1 reads `a` in place (args_in_place).  What every step reads of it
-    // (cps, side_key, cap) the compiler hoists out of the op loop itself;
+    // (side_key, cap) the compiler hoists out of the op loop itself;
     // text_base is first read under the step's insert branch and would be
     // loaded there, on every insert, so it is read once here
     const uint32_t text_base = a.text_base;
     asm volatile("" ::"s"(text_base));
+    if constexpr (E <= kBlockEmax) {
+      // likewise cps in the block tiers (pass 1 alone runs them): under the
+      // insert and annotate branches it was a load, a wait and then the
+      // dependent load of the set, on every insert with a set and every
+      // annotate that marks something
+      const uint4* const cps = a.cps;
+      asm volatile("" ::"s"(cps));
+    }
   }
   load_regs<E, K>(R, D, a);
   const uint32_t kend = D.k1 - D.k > limit ? D.k + limit : D.k1;

@@ -30,6 +30,17 @@
 
 namespace mte {
 
+// MTE_PASS1_UNIT is defined by mte_pass_pair.hip alone.  The step is shared
+// with pass 2 (big_kernel runs doc_step_v at E = 4) and the chunk pass, whose
+// units are compiled as before; what is written for pass 1's own compile
+// (its unit leaves wave-uniform branches unstructurized, Makefile) is under
+// this constant, so the other units' device code does not move with it.
+#ifdef MTE_PASS1_UNIT
+constexpr bool kPass1Unit = true;
+#else
+constexpr bool kPass1Unit = false;
+#endif
+
 // number of set bits of m in the lanes below this one
 __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -293,8 +304,21 @@ __device__ __forceinline__ int seg_op_v(Regs<E, K>& R, int& n, const s8v& op, co
 #pragma unroll
       for (int j = 0; j < E; j++) {
         const bool own = fget(sp, j), tl = fget(tail, j);
-        R.len[j] = own ? X[0][j] : (tl ? R.len[j] - X[0][j] : R.len[j]);
-        R.toff[j] = tl ? R.toff[j] + (uint32_t)X[0][j] : R.toff[j];
+        if constexpr (!kPass1Unit) {
+          R.len[j] = own ? X[0][j] : (tl ? R.len[j] - X[0][j] : R.len[j]);
+          R.toff[j] = tl ? R.toff[j] + (uint32_t)X[0][j] : R.toff[j];
+        } else {
+          // pass 1: the same selects with both arms in locals.  A ternary with
+          // arithmetic in an arm is emitted as a branch, and at E >= 2 those
+          // lane-divergent branches stayed branches, which put the whole insert
+          // path through the CFG structurizer and its flow blocks' copies of the
+          // planes (DESIGN §6 "Uniform branches left unstructurized")
+          const int32_t x = X[0][j], len = R.len[j], rest = len - x;
+          const uint32_t off = R.toff[j], moved = off + (uint32_t)x;
+          const int32_t kept = tl ? rest : len;
+          R.len[j] = own ? x : kept;
+          R.toff[j] = tl ? moved : off;
+        }
       }
       at = nb & ins;
       n += nlen > 0 ? 2 : 1;

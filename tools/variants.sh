@@ -10,16 +10,21 @@
 set -e
 cd "$(dirname "$0")/.."
 OBJ=fluidframework_amd/_lib/obj
+PAIR_FLAGS=$(make -s -C fluidframework_amd/csrc pair-flags)
 rm -rf build_var
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   mkdir -p build_var/$name
   ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $flags -c \
       -o build_var/$name/flat.o fluidframework_amd/csrc/mte_pass_flat.hip &&
+    # pass 1's unit with the product build's own option for it
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $PAIR_FLAGS $flags -c \
+      -o build_var/$name/pair.o fluidframework_amd/csrc/mte_pass_pair.hip &&
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $flags -c \
       -o build_var/$name/chunk.o fluidframework_amd/csrc/mte_pass_chunk.hip &&
     /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -shared -o build_var/$name/libmte.so \
-      $OBJ/mte_engine.o $OBJ/mte_pass_tree.o $OBJ/mte_pass_htree.o build_var/$name/flat.o build_var/$name/chunk.o $OBJ/mte_build.o \
+      $OBJ/mte_engine.o $OBJ/mte_pass_tree.o $OBJ/mte_pass_htree.o build_var/$name/pair.o build_var/$name/flat.o build_var/$name/chunk.o \
+      $OBJ/mte_query.o $OBJ/mte_build.o \
       -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib ) &
 done
 wait
