@@ -25,9 +25,9 @@
 // advances, and when a chunk op could overflow its 256 slots; the pass ends
 // with a final gather, so every other kernel sees the flat layout.
 #pragma once
-
 #include "mte_passes.h"
-#include "mte_replay.h"
+#include "mte_docrun.h"
+#include "mte_step1.h"
 
 namespace mte {
 
@@ -517,7 +517,7 @@ __device__ int ch_ops(DocRun& D, const ReplayArgs& a, const ChunkArgs& ch, uint3
       st[kStChunkScan] += scan;
     })
     D.k++;
-    // collab window (doc_step, mte_replay.h)
+    // collab window (doc_step, mte_step8.h)
     const bool live = type != MTE_OP_NOOP, end = (flags & MTE_F_MSG_END) != 0;
     const bool bad = (live & (s <= D.cur_seq)) | (end & (s < D.cur_seq)) | ((live | end) & (msn < D.min_seq)) |
                      (end & (msn > s));

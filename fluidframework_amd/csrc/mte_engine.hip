@@ -652,7 +652,7 @@ struct DocState {
   // the flat HBM-streamed pass's own documents (new length calc with delta
   // events, no local client): BatchSlot::sorder
   std::vector<uint32_t> h_sdocs;
-  // local references of the MTE_DOC_REFS documents (mte_stream.h): ref_cap slots
+  // local references of the MTE_DOC_REFS documents (mte_hbm.h): ref_cap slots
   // per document, zeroed at every reset
   std::vector<uint32_t> h_ref_hi;   // per doc: reference slots its MTE_OP_REF records used so far (+1)
   uint2* d_refs = nullptr;

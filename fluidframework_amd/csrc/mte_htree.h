@@ -26,12 +26,13 @@
 // (lengths, searches, moves, compactions) run across the wave, the tree's
 // bookkeeping (splits, LRU heap, scour's append chain, packParent) as uniform
 // scalar code over single-item loads.  Loads bypass L1 (ld_l2) and every phase
-// that stores ends with vm_drain, as in mte_stream.h.
+// that stores ends with vm_drain (mte_hbm.h), as in mte_stream.h.
 #pragma once
 
 #include "mte_passes.h"
-#include "mte_stream.h"
-#include "mte_tree.h"
+#include "mte_docrun.h"
+#include "mte_hbm.h"
+#include "mte_treeword.h"
 
 namespace mte {
 

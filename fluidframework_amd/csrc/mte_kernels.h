@@ -151,7 +151,7 @@ struct ReplayArgs {
   uint32_t* dl_n;
   // MTE_DOC_REFS documents: local reference slots of doc d at refs[d * ref_cap ..]
   // (x = the arena offset of the unit the reference sits on, y = kRefLive |
-  // kRefDetached | refType; mte_stream.h)
+  // kRefDetached | refType; mte_hbm.h)
   uint2* refs;
   uint32_t ref_cap;
   // the streamed pass's document order (stream_kernel: wave i replays document

@@ -103,7 +103,7 @@ constexpr int local_planes(int K) { return kFieldPlanes + 3 * K + 6; }
 constexpr int rm_hi_plane(int K) { return local_planes(K) - 1; }
 template <int K> constexpr int kLocalPlanes = local_planes(K);
 
-// ---- local references (MTE_DOC_REFS, include/mte.h; mte_stream.h) -----------
+// ---- local references (MTE_DOC_REFS, include/mte.h; mte_hbm.h) --------------
 // A reference is kept as the text unit it sits on -- its arena offset (a
 // marker's is its reserved unit): splits never copy text, so the unit names the
 // same place in whatever segment holds it, which is what LocalReferenceCollection

@@ -2,7 +2,7 @@
 // per lane, documents of <= 254 segments: nearly every op of a conflict-farm
 // batch).
 //
-// Same semantics as doc_step (mte_replay.h, which cites the reference for
+// Same semantics as doc_step (mte_step8.h, which cites the reference for
 // every rule), but the split / insert decisions stay per slot instead of
 // going through scalar lookups: a slot learns "I am after the split leaf"
 // from the popcount of the candidate ballot in the lanes below (v_mbcnt) plus
@@ -27,6 +27,8 @@
 #pragma once
 
 #include "mte_kernels.h"
+#include "mte_docrun.h"
+#include "mte_regdoc.h"
 
 namespace mte {
 
@@ -40,11 +42,6 @@ constexpr bool kPass1Unit = true;
 #else
 constexpr bool kPass1Unit = false;
 #endif
-
-// number of set bits of m in the lanes below this one
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // ---- per-slot flags ----------------------------------------------------------
 // A per-slot flag is one bit of an integer held per lane: bit j of the word is

@@ -30,13 +30,11 @@
 #pragma once
 
 #include "mte_passes.h"
-#include "mte_replay.h"
+#include "mte_docrun.h"
+#include "mte_regdoc.h"
+#include "mte_treeword.h"
 
 namespace mte {
-
-constexpr uint32_t kNsUndef = 0, kNsFalse = 1, kNsTrue = 2;
-constexpr int kMaxNodes = 8;       // MaxNodesInBlock, mergeTreeNodes.ts:373
-constexpr int32_t kTextGranularity = 256;  // textSegment.ts:19
 
 // MTE_TREE_PROF (a profiling build only, `make prof`): with statistics on, the
 // tree pass's counters become phase clocks (s_memrealtime ticks, 100 MHz):
@@ -50,10 +48,6 @@ constexpr int32_t kTextGranularity = 256;  // textSegment.ts:19
 #define TSTAT(...) MTE_STAT(__VA_ARGS__)
 #define TPROF(...)
 #endif
-
-__device__ __forceinline__ uint32_t t_h(uint32_t t) { return t & kTH; }
-__device__ __forceinline__ uint32_t t_ns(uint32_t t) { return (t & kTNs) >> kTNsShift; }
-__device__ __forceinline__ uint32_t t_id(uint32_t t) { return (t >> 8) & (kIdLimit - 1u); }
 
 // ---- wave-wide index helpers (E slots per lane, index = lane * E + j) --------
 

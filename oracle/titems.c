@@ -1095,7 +1095,7 @@ static int doc_ref(idoc* d, const mte_op* op) {
  * the reference's beforeSlide / afterSlide callbacks, localReference.ts:436-447) */
 static int delta_push(idoc* d, uint32_t kind, int64_t pos, int32_t len, uint32_t removed);
 static int64_t own_prefix(const idoc* d, uint32_t at);
-/* mode (mte_stream.h stream_slide): 0 every such item; 1 the removals of one
+/* mode (mte_hbm.h stream_slide): 0 every such item; 1 the removals of one
  * ack, in order, each slid while the later ones are still pending
  * (ackPendingSegment, mergeTree.ts:1285-1304: a reference can slide again);
  * 2 / 3 a remote remove's items the local client had removed already (lrs),

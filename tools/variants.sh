@@ -4,8 +4,9 @@
 # and chunk-pass translation units are rebuilt with the variant's flags and
 # linked with the product's other objects (make -C fluidframework_amd/csrc first).
 # The knobs are the build-time macros of mte_replay.h (MTE_PAIR_WAVES, MTE_BURST,
-# MTE_PASS1_EMAX) and the diagnostic switches of the other passes; the rejected
-# variants DESIGN.md measures were removed after commit 15e7501.
+# MTE_PASS1_EMAX) and the diagnostic switches of the other passes.  The rejected
+# kernels DESIGN.md §6 measures (mte_lean.h, mte_rsmall.h) are not in the tree:
+# tools/variants/ held them last at commit 58eea73.
 # Usage: variants.sh name:"flags" ...   e.g. variants.sh w5e2:"-DMTE_PASS1_EMAX=2"
 set -e
 cd "$(dirname "$0")/.."
