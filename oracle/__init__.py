@@ -1,5 +1,6 @@
-"""Python binding of the CPU restatements (oracle/oracle.c flat, oracle/tree.c
-tree-exact).
+"""Python binding of the four CPU restatements: oracle/oracle.c (flat),
+tree.c (tree-exact), titems.c (the tree on an item array) and chunked.c (flat
+with a chunk index), one class over their common C surface (orc_shell.h).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, always as the checker / the timed CPU baseline,
@@ -11,7 +12,7 @@ import subprocess
 
 import numpy as np
 
-from fluidframework_amd.abi import DOC_INIT_DTYPE, DOC_LOCAL_CLIENT, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE, ptr  # noqa: F401
+from fluidframework_amd.abi import DOC_INIT_DTYPE, DOC_LOCAL_CLIENT, MTE_E_UNSUPPORTED, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE, ptr  # noqa: F401
 from fluidframework_amd.engine import EngineBase, _arr, make_batch_struct
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +24,24 @@ def build():
     subprocess.check_call(["make", "-s", "-C", HERE])
 
 
+def _signatures():
+    """name -> argtypes of `<prefix>_<name>` (all return int)."""
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    return {
+        "create": [u32, vp], "destroy": [vp],
+        "load_docs": [vp, u32, vp, vp, u64, vp, u32, vp, u32], "load_segments": [vp, vp, vp, u64],
+        "apply_batch": [vp, vp, C.c_int],
+        "read_doc": [vp, u32, vp], "read_segments": [vp, u32, vp], "digest": [vp, vp, u32],
+        "doc_status": [vp, vp, u32], "stats_get": [vp, vp], "doc_nsegs": [vp, u32, vp],
+        "doc_shape": [vp, u32, C.c_char_p, u32], "set_limit": [vp, u32],
+        "read_deltas": [vp, u32, vp, u64, vp], "read_refs": [vp, u32, vp, u32],
+        "read_refs_transient": [vp, u32, vp, u32], "read_ref_order": [vp, u32, vp, u32],
+    }
+
+
+PREFIXES = ("orc", "ort", "oti", "och")  # oracle.c, tree.c, titems.c, chunked.c
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -30,59 +49,26 @@ def load():
     if not os.path.exists(LIB):
         build()
     lib = C.CDLL(LIB)
-    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    for pre in ("orc", "ort"):
-        for name, args in {
-            "create": [u32, vp], "destroy": [vp],
-            "load_docs": [vp, u32, vp, vp, u64, vp, u32, vp, u32],
-            "load_segments": [vp, vp, vp, u64],
-            "read_segments": [vp, u32, vp],
-            "apply_batch": [vp, vp, C.c_int], "read_doc": [vp, u32, vp],
-            "digest": [vp, vp, u32], "doc_status": [vp, vp, u32],
-            "stats_get": [vp, vp], "doc_nsegs": [vp, u32, vp],
-        }.items():
-            f = getattr(lib, f"{pre}_{name}")
-            f.argtypes = args
-            f.restype = C.c_int
-    for name, args in {
-        "oti_create": [u32, vp], "oti_destroy": [vp],
-        "oti_load_docs": [vp, u32, vp, vp, u64, vp, u32, vp, u32],
-        "oti_load_segments": [vp, vp, vp, u64], "oti_apply_batch": [vp, vp, C.c_int],
-        "oti_read_doc": [vp, u32, vp], "oti_digest": [vp, vp, u32], "oti_doc_status": [vp, vp, u32],
-        "oti_doc_nsegs": [vp, u32, vp], "oti_stats_get": [vp, vp], "oti_read_segments": [vp, u32, vp], "oti_set_limit": [vp, u32],
-        "oti_read_deltas": [vp, u32, vp, u64, vp], "oti_read_refs": [vp, u32, vp, u32], "oti_read_refs_transient": [vp, u32, vp, u32], "oti_read_ref_order": [vp, u32, vp, u32],
-        "och_create": [u32, vp], "och_destroy": [vp], "och_load_docs": [vp, u32, vp, vp, u64, vp, u32, vp, u32],
-        "och_load_segments": [vp, vp, vp, u64], "och_apply_batch": [vp, vp, C.c_int], "och_read_doc": [vp, u32, vp],
-        "och_digest": [vp, vp, u32], "och_doc_status": [vp, vp, u32], "och_doc_nsegs": [vp, u32, vp],
-        "och_stats_get": [vp, vp], "och_read_segments": [vp, u32, vp],
-    }.items():
-        f = getattr(lib, name)
-        f.argtypes = args
-        f.restype = C.c_int
-    lib.orc_read_deltas.argtypes = [vp, u32, vp, u64, vp]
-    lib.orc_read_deltas.restype = C.c_int
-    lib.orc_read_refs.argtypes = [vp, u32, vp, u32]
-    lib.orc_read_refs.restype = C.c_int
-    lib.orc_read_refs_transient.argtypes = [vp, u32, vp, u32]
-    lib.orc_read_refs_transient.restype = C.c_int
-    lib.orc_read_ref_order.argtypes = [vp, u32, vp, u32]
-    lib.orc_read_ref_order.restype = C.c_int
-    for pre in ("ort", "oti"):
-        f = getattr(lib, f"{pre}_doc_shape")
-        f.argtypes = [vp, u32, C.c_char_p, u32]
-        f.restype = C.c_int
+    for name, args in _signatures().items():  # one table, applied to what each restatement exports
+        for pre in PREFIXES:
+            f = getattr(lib, f"{pre}_{name}", None)
+            if f is not None:
+                f.argtypes = args
+                f.restype = C.c_int
     _lib = lib
     return lib
 
 
 class _Fn:
-    """lib.<prefix>_<name> lookups for one restatement."""
+    """lib.<prefix>_<name> lookups for one restatement.  A function it does
+    not export answers MTE_E_UNSUPPORTED: no other restatement's function is
+    ever called on this one's context."""
 
     def __init__(self, lib, pre):
         self.lib, self.pre = lib, pre
 
     def __getattr__(self, name):
-        return getattr(self.lib, f"{self.pre}_{name}")
+        return getattr(self.lib, f"{self.pre}_{name}", None) or (lambda *a: MTE_E_UNSUPPORTED)
 
 
 class OracleEngine(EngineBase):
@@ -114,6 +100,8 @@ class OracleEngine(EngineBase):
         """(tree shape string, LRU heap size) of one document (tree=True only)."""
         buf = C.create_string_buffer(1 << 16)
         hn = self.f.doc_shape(self.ctx, doc, buf, len(buf))
+        if hn < 0:
+            self._check(hn, "shape")
         return buf.value.decode(), hn
 
     def __del__(self):
@@ -154,8 +142,7 @@ class OracleEngine(EngineBase):
         return self.f.read_doc(self.ctx, doc, vptr)
 
     def _read_deltas(self, doc, p, cap, np_):
-        f = self.lib.oti_read_deltas if self.tree == "items" else self.lib.orc_read_deltas
-        return f(self.ctx, doc, p, cap, np_)
+        return self.f.read_deltas(self.ctx, doc, p, cap, np_)
 
     def set_event_capacity(self, per_op):
         """The restatement's event buffers grow as needed (mte_set_event_capacity's bound is the engine's)."""
@@ -166,13 +153,11 @@ class OracleEngine(EngineBase):
         self.ref_capacity = int(per_doc)
 
     def _read_refs(self, doc, p, n, transient=False):
-        pre = "oti" if self.tree == "items" else "orc"
-        return getattr(self.lib, f"{pre}_read_refs{'_transient' if transient else ''}")(self.ctx, doc, p, n)
+        return (self.f.read_refs_transient if transient else self.f.read_refs)(self.ctx, doc, p, n)
 
     def read_ref_order(self, doc, n):
-        f = self.lib.oti_read_ref_order if self.tree == "items" else self.lib.orc_read_ref_order
         out = np.zeros(max(n, 1), np.int64)
-        self._check(f(self.ctx, doc, ptr(out), n), "read_ref_order")
+        self._check(self.f.read_ref_order(self.ctx, doc, ptr(out), n), "read_ref_order")
         return out[:n]
 
     def _digest(self, p, n):

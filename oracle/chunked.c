@@ -26,14 +26,16 @@
  * Only remote (observer) replay with the new length calculation: the config-5
  * documents.  Other documents are refused (MTE_E_UNSUPPORTED).
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg load it.
+ *
+ * The replay rules end at the API banner below; under it is glue over the shell
+ * the four restatements share (orc_shell.h: arena, load tables, load and batch
+ * validation, thread pool, read-out emitters).  What this file does differently
+ * from the other three stands there once, at its call site, with a comment.
  */
 #include <limits.h>
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "chunked.h"
-#include "orc_common.h"
+#include "orc_shell.h"
 
 #define NONE_SEQ ORC_NONE_SEQ
 #define CH 512           /* segments per chunk at most */
@@ -71,12 +73,8 @@ typedef struct {
 struct och_ctx {
   uint32_t n_keys, n_docs;
   cdoc* docs;
-  uint16_t* arena;
-  uint64_t arena_n, arena_cap, load_units;
-  mte_propset* load_ps;
-  uint32_t n_load_ps;
-  mte_prop* load_pe;
-  uint32_t n_load_pe;
+  orc_arena arena;
+  orc_load_tables load;
 };
 
 /* ---- lengths (oracle.c leaf_len, new calculation) -------------------------- */
@@ -400,21 +398,6 @@ static int doc_apply(cdoc* d, const mte_op* op, const env_t* env) {
 
 /* ---- API --------------------------------------------------------------------------------- */
 
-static int arena_append(och_ctx* c, const uint16_t* t, uint64_t n, uint64_t* base) {
-  if (c->arena_n + n > c->arena_cap) {
-    uint64_t nc = c->arena_cap ? c->arena_cap : 1024;
-    while (nc < c->arena_n + n) nc *= 2;
-    uint16_t* a = (uint16_t*)realloc(c->arena, nc * sizeof(uint16_t));
-    if (!a) return MTE_E_OOM;
-    c->arena = a;
-    c->arena_cap = nc;
-  }
-  *base = c->arena_n;
-  if (n) memcpy(c->arena + c->arena_n, t, n * sizeof(uint16_t));
-  c->arena_n += n;
-  return MTE_OK;
-}
-
 int och_create(uint32_t n_keys, och_ctx** out) {
   if (!out || n_keys > MTE_MAX_KEYS) return MTE_E_INVALID_ARG;
   och_ctx* c = (och_ctx*)calloc(1, sizeof(och_ctx));
@@ -434,18 +417,15 @@ static void free_doc(cdoc* d) {
 static void free_docs(och_ctx* c) {
   for (uint32_t i = 0; i < c->n_docs; i++) free_doc(&c->docs[i]);
   free(c->docs);
-  free(c->load_ps);
-  free(c->load_pe);
   c->docs = NULL;
-  c->load_ps = NULL;
-  c->load_pe = NULL;
   c->n_docs = 0;
+  orc_load_tables_free(&c->load);
 }
 
 int och_destroy(och_ctx* c) {
   if (!c) return MTE_E_INVALID_ARG;
   free_docs(c);
-  free(c->arena);
+  free(c->arena.p);
   free(c);
   return MTE_OK;
 }
@@ -473,35 +453,23 @@ int och_load_docs(och_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
                   const mte_propset* propsets, uint32_t n_propsets, const mte_prop* props, uint32_t n_props) {
   if (!c || (n_docs && !docs)) return MTE_E_INVALID_ARG;
   free_docs(c);
-  c->arena_n = 0;
+  c->arena.n = 0;
   uint64_t base = 0;
-  int rc = arena_append(c, text, text_units, &base);
+  int rc = orc_arena_append(&c->arena, text, text_units, &base);
   if (rc) return rc;
-  c->load_units = text_units;
-  c->docs = (cdoc*)aligned_alloc(128, (size_t)(n_docs ? n_docs : 1) * sizeof(cdoc));
-  if (!c->docs) return MTE_E_OOM;
-  memset(c->docs, 0, (size_t)(n_docs ? n_docs : 1) * sizeof(cdoc));
+  if (!(c->docs = (cdoc*)orc_docs_alloc(n_docs, sizeof(cdoc)))) return MTE_E_OOM;
   c->n_docs = n_docs;
-  if (n_propsets) {
-    c->load_ps = (mte_propset*)malloc((size_t)n_propsets * sizeof(mte_propset));
-    if (!c->load_ps) return MTE_E_OOM;
-    memcpy(c->load_ps, propsets, (size_t)n_propsets * sizeof(mte_propset));
-    c->n_load_ps = n_propsets;
-  }
-  if (n_props) {
-    c->load_pe = (mte_prop*)malloc((size_t)n_props * sizeof(mte_prop));
-    if (!c->load_pe) return MTE_E_OOM;
-    memcpy(c->load_pe, props, (size_t)n_props * sizeof(mte_prop));
-    c->n_load_pe = n_props;
-  }
+  if ((rc = orc_load_tables_copy(&c->load, propsets, n_propsets, props, n_props, text_units))) return rc;
   for (uint32_t i = 0; i < n_docs; i++) {
     cdoc* d = &c->docs[i];
     const mte_doc_init* in = &docs[i];
-    if ((uint64_t)in->text_off + in->text_len > text_units) return MTE_E_INVALID_ARG;
+    if ((rc = orc_init_text_check(in, text_units))) return rc;
     d->init = *in;
     d->flags = in->flags;
     d->min_seq = in->min_seq;
     d->cur_seq = in->cur_seq;
+    /* a document this restatement does not replay (legacy calculation, local
+     * client, events) stops alone; the load goes on (oracle.c refuses the load) */
     if (!(in->flags & MTE_DOC_NEW_LENGTH_CALC) || (in->flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS)))
       d->status = MTE_E_UNSUPPORTED;
     cseg g;
@@ -520,8 +488,7 @@ int och_load_docs(och_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
 }
 
 int och_load_segments(och_ctx* c, const uint64_t* seg_offsets, const mte_seg* segs, uint64_t n_segs) {
-  if (!c || !seg_offsets || (n_segs && !segs)) return MTE_E_INVALID_ARG;
-  if (seg_offsets[0] != 0 || seg_offsets[c->n_docs] != n_segs) return MTE_E_INVALID_ARG;
+  if (!c || orc_seg_offsets_check(seg_offsets, c->n_docs, segs, n_segs)) return MTE_E_INVALID_ARG;
   for (uint32_t di = 0; di < c->n_docs; di++) {
     const uint64_t b = seg_offsets[di], e = seg_offsets[di + 1];
     if (e < b) return MTE_E_INVALID_ARG;
@@ -529,32 +496,15 @@ int och_load_segments(och_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
     const uint32_t n = (uint32_t)(e - b);
     cseg* tmp = (cseg*)calloc(n, sizeof(cseg));
     if (!tmp) return MTE_E_OOM;
+    int rc = MTE_OK;
     for (uint32_t k = 0; k < n; k++) {
-      const mte_seg* sg = &segs[b + k];
-      const int marker = sg->kind != 0;
-      if ((marker && sg->len != 1) || (!marker && (sg->len == 0 || (uint64_t)sg->text_off + sg->len > c->load_units)) ||
-          sg->client < -1 || sg->client >= MTE_MAX_CLIENTS || sg->seq < 0 ||
-          (sg->removed_seq != MTE_NOT_REMOVED && sg->removers == 0)) {
-        free(tmp);
-        return MTE_E_INVALID_ARG;
-      }
-      cseg* g = &tmp[k];
-      g->len = (int32_t)sg->len;
-      g->seq = sg->seq;
-      g->cli = sg->client;
-      g->rseq = sg->removed_seq == MTE_NOT_REMOVED ? NONE_SEQ : sg->removed_seq;
-      g->rmask = sg->removed_seq == MTE_NOT_REMOVED ? 0u : sg->removers;
-      g->kind = sg->kind;
-      g->toff = marker ? 0u : sg->text_off;
-      if (sg->propset != MTE_NO_PROPS) {
-        if (sg->propset >= c->n_load_ps) {
-          free(tmp);
-          return MTE_E_INVALID_ARG;
-        }
-        orc_apply_props(g->props, c->n_keys, &c->load_ps[sg->propset], c->load_pe, 0);
-      }
+      orc_seg_fields f;
+      if ((rc = orc_seg_in(&segs[b + k], &c->load, &f))) break;
+      ORC_SEG_TAKE(&tmp[k], f);
+      tmp[k].toff = f.toff;
+      orc_seg_in_props(&segs[b + k], &c->load, tmp[k].props, c->n_keys);
     }
-    const int rc = doc_from(&c->docs[di], tmp, n);
+    if (!rc) rc = doc_from(&c->docs[di], tmp, n);
     free(tmp);
     if (rc) return rc;
   }
@@ -565,59 +515,33 @@ typedef struct {
   och_ctx* c;
   const mte_batch* b;
   uint64_t base;
-  uint32_t d0, d1, stride;
-} worker_arg;
+} batch_arg;
 
-static void* worker(void* p) {
-  worker_arg* w = (worker_arg*)p;
+/* one document's records: remote ones only, no MTE_OP_RELPOS stepping */
+static void apply_doc(void* p, uint32_t di) {
+  const batch_arg* w = (const batch_arg*)p;
   env_t env = {w->b, w->base, w->c->n_keys};
-  for (uint32_t di = w->d0; di < w->d1; di += w->stride) {
-    cdoc* d = &w->c->docs[di];
-    if (d->status) continue;
-    for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
-      const int rc = doc_apply(d, &w->b->ops[k], &env);
-      if (rc) {
-        d->status = rc;
-        break;
-      }
+  cdoc* d = &w->c->docs[di];
+  if (d->status) return;
+  for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
+    const int rc = doc_apply(d, &w->b->ops[k], &env);
+    if (rc) {
+      d->status = rc;
+      break;
     }
   }
-  return NULL;
 }
 
 int och_apply_batch(och_ctx* c, const mte_batch* b, int n_threads) {
-  if (!c || !b || b->n_docs != c->n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
-  if (b->op_offsets[b->n_docs] != b->n_ops) return MTE_E_INVALID_ARG;
-  for (uint64_t k = 0; k < b->n_ops; k++) {
-    const mte_op* op = &b->ops[k];
-    if (op->type == MTE_OP_INSERT && !(op->flags & MTE_F_MARKER) && op->pos2 > 0 &&
-        (uint64_t)op->a + (uint64_t)op->pos2 > b->text_units)
-      return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_INSERT && op->b != MTE_NO_PROPS && op->b >= b->n_propsets) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_ANNOTATE && op->a >= b->n_propsets) return MTE_E_INVALID_ARG;
-  }
-  uint64_t base = 0;
-  int rc = arena_append(c, b->text, b->text_units, &base);
+  if (!c) return MTE_E_INVALID_ARG;
+  /* no document flags: a local-client document stopped at its load, and a
+   * record this restatement does not replay stops its document in doc_apply */
+  int rc = orc_check_batch(b, c->n_docs, NULL, 0);
   if (rc) return rc;
-  if (n_threads < 1) n_threads = 1;
-  if ((uint32_t)n_threads > c->n_docs) n_threads = c->n_docs ? (int)c->n_docs : 1;
-  worker_arg* args = (worker_arg*)calloc((size_t)n_threads, sizeof(worker_arg));
-  pthread_t* th = (pthread_t*)calloc((size_t)n_threads, sizeof(pthread_t));
-  if (!args || !th) {
-    free(args);
-    free(th);
-    return MTE_E_OOM;
-  }
-  for (int t = 0; t < n_threads; t++) args[t] = (worker_arg){c, b, base, (uint32_t)t, c->n_docs, (uint32_t)n_threads};
-  if (n_threads == 1) {
-    worker(&args[0]);
-  } else {
-    for (int t = 0; t < n_threads; t++) pthread_create(&th[t], NULL, worker, &args[t]);
-    for (int t = 0; t < n_threads; t++) pthread_join(th[t], NULL);
-  }
-  free(args);
-  free(th);
-  return MTE_OK;
+  batch_arg w = {c, b, 0};
+  if ((rc = orc_arena_append(&c->arena, b->text, b->text_units, &w.base))) return rc;
+  /* its one statistic, the records applied, runs on over the batches */
+  return orc_run_docs(n_threads, c->n_docs, apply_doc, &w);
 }
 
 int och_digest(och_ctx* c, uint64_t* out, uint32_t n_docs) {
@@ -630,13 +554,10 @@ int och_digest(och_ctx* c, uint64_t* out, uint32_t n_docs) {
       for (uint32_t i = 0; i < ck->n; i++) {
         const cseg* g = &ck->s[i];
         if (g->rseq != NONE_SEQ) continue;
-        orc_digest_seg(&acc, g->kind, g->kind == 0 ? c->arena + g->toff : NULL, g->len, g->props, c->n_keys);
+        orc_digest_seg(&acc, g->kind, g->kind == 0 ? c->arena.p + g->toff : NULL, g->len, g->props, c->n_keys);
       }
     }
-    out[4 * (size_t)di + 0] = acc.n;
-    out[4 * (size_t)di + 1] = acc.h1;
-    out[4 * (size_t)di + 2] = acc.h2;
-    out[4 * (size_t)di + 3] = acc.sum;
+    orc_digest_out(out, di, &acc);
   }
   return MTE_OK;
 }
@@ -658,31 +579,15 @@ int och_doc_nsegs(och_ctx* c, uint32_t doc, uint32_t* out) {
 int och_read_doc(och_ctx* c, uint32_t doc, mte_doc_view* v) {
   if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
   const cdoc* d = &c->docs[doc];
-  v->status = d->status;
-  v->cur_seq = d->cur_seq;
-  v->min_seq = d->min_seq;
-  uint32_t length = 0, nt = 0, ns = 0;
+  orc_view_begin(v, d->status, d->cur_seq, d->min_seq);
   for (uint32_t k = 0; k < d->nch; k++) {
     const chunk* ck = d->ch[k];
     for (uint32_t i = 0; i < ck->n; i++) {
       const cseg* g = &ck->s[i];
       if (g->rseq != NONE_SEQ) continue;
-      if (ns < v->seg_cap) {
-        if (v->seg_len) v->seg_len[ns] = (uint32_t)g->len;
-        if (v->seg_kind) v->seg_kind[ns] = g->kind;
-        if (v->seg_props)
-          for (uint32_t q = 0; q < c->n_keys; q++) v->seg_props[(size_t)ns * c->n_keys + q] = g->props[q];
-      }
-      ns++;
-      length += (uint32_t)g->len;
-      if (g->kind == 0)
-        for (int32_t u = 0; u < g->len; u++, nt++)
-          if (nt < v->text_cap && v->text) v->text[nt] = c->arena[g->toff + (uint32_t)u];
+      orc_view_seg(v, c->n_keys, g->kind, g->len, g->props, g->kind == 0 ? c->arena.p + g->toff : NULL, 0);
     }
   }
-  v->length = length;
-  v->n_text = nt;
-  v->n_segs = ns;
   return MTE_OK;
 }
 
@@ -691,32 +596,14 @@ int och_read_doc(och_ctx* c, uint32_t doc, mte_doc_view* v) {
 int och_read_segments(och_ctx* c, uint32_t doc, mte_seg_list* v) {
   if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
   const cdoc* d = &c->docs[doc];
-  uint64_t nt = 0;
-  uint32_t i = 0;
+  orc_segs_begin(v);
   for (uint32_t k = 0; k < d->nch; k++) {
     const chunk* ck = d->ch[k];
-    for (uint32_t j = 0; j < ck->n; j++, i++) {
+    for (uint32_t j = 0; j < ck->n; j++) {
       const cseg* g = &ck->s[j];
-      if (i < v->seg_cap && v->segs) {
-        mte_seg* s = &v->segs[i];
-        s->text_off = g->kind == 0 ? (uint32_t)nt : 0u;
-        s->len = (uint32_t)g->len;
-        s->seq = g->seq;
-        s->removed_seq = g->rseq == NONE_SEQ ? MTE_NOT_REMOVED : g->rseq;
-        s->removers = g->rseq == NONE_SEQ ? 0u : g->rmask;
-        s->client = g->cli;
-        s->kind = g->kind;
-        s->propset = MTE_NO_PROPS;
-        if (v->props)
-          for (uint32_t q = 0; q < c->n_keys; q++) v->props[(size_t)i * c->n_keys + q] = g->props[q];
-      }
-      if (g->kind == 0)
-        for (int32_t u = 0; u < g->len; u++, nt++)
-          if (nt < v->text_cap && v->text) v->text[nt] = c->arena[g->toff + (uint32_t)u];
+      orc_segs_seg(v, c->n_keys, ORC_SEG_GIVE(g), g->props, g->kind == 0 ? c->arena.p + g->toff : NULL, 0);
     }
   }
-  v->n_segs = i;
-  v->n_text = nt;
   return MTE_OK;
 }
 

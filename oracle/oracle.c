@@ -11,14 +11,16 @@
  * pin it.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it.
+ *
+ * The replay rules end at the API banner below; under it is glue over the shell
+ * the four restatements share (orc_shell.h: arena, load tables, load and batch
+ * validation, thread pool, read-out emitters).  What this file does differently
+ * from the other three stands there once, at its call site, with a comment.
  */
 #include "oracle.h"
-#include "orc_common.h"
+#include "orc_shell.h"
 
 #include <limits.h>
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
 
 #define NONE_SEQ ORC_NONE_SEQ
 
@@ -71,31 +73,11 @@ struct orc_ctx {
   uint32_t n_keys;
   uint32_t n_docs;
   odoc* docs;
-  uint64_t load_units;     /* text units given to orc_load_docs */
-  mte_propset* load_ps;    /* propsets given to orc_load_docs (for orc_load_segments) */
-  uint32_t n_load_ps;
-  mte_prop* load_pe;
-  uint32_t n_load_pe;
-  uint16_t* arena;
-  uint64_t arena_n, arena_cap;
+  orc_load_tables load; /* what orc_load_docs was given (for orc_load_segments) */
+  orc_arena arena;
 };
 
 /* ------------------------------------------------------------------------ */
-
-static int arena_append(orc_ctx* c, const uint16_t* t, uint64_t n, uint64_t* base) {
-  if (c->arena_n + n > c->arena_cap) {
-    uint64_t nc = c->arena_cap ? c->arena_cap : 1024;
-    while (nc < c->arena_n + n) nc *= 2;
-    uint16_t* a = (uint16_t*)realloc(c->arena, nc * sizeof(uint16_t));
-    if (!a) return MTE_E_OOM;
-    c->arena = a;
-    c->arena_cap = nc;
-  }
-  *base = c->arena_n;
-  if (n) memcpy(c->arena + c->arena_n, t, n * sizeof(uint16_t));
-  c->arena_n += n;
-  return MTE_OK;
-}
 
 /* a pk row: MTE_MAX_KEYS pending-key localSeqs, the mask of the pending
  * annotate groups (MTE_ANNOTATE_SLOTS) the segment belongs to, then per key the
@@ -893,7 +875,7 @@ static int doc_apply(odoc* d, const mte_op* op, const apply_env* env) {
   return MTE_OK;
 }
 
-/* ------------------------------------------------------------------------ */
+/* ---- API --------------------------------------------------------------- */
 
 int orc_create(uint32_t n_keys, orc_ctx** out) {
   if (!out || n_keys > MTE_MAX_KEYS) return MTE_E_INVALID_ARG;
@@ -917,17 +899,13 @@ static void free_docs(orc_ctx* c) {
   free(c->docs);
   c->docs = NULL;
   c->n_docs = 0;
-  free(c->load_ps);
-  free(c->load_pe);
-  c->load_ps = NULL;
-  c->load_pe = NULL;
-  c->n_load_ps = c->n_load_pe = 0;
+  orc_load_tables_free(&c->load);
 }
 
 int orc_destroy(orc_ctx* c) {
   if (!c) return MTE_E_INVALID_ARG;
   free_docs(c);
-  free(c->arena);
+  free(c->arena.p);
   free(c);
   return MTE_OK;
 }
@@ -935,36 +913,24 @@ int orc_destroy(orc_ctx* c) {
 int orc_load_docs(orc_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const uint16_t* text,
                   uint64_t text_units, const mte_propset* propsets, uint32_t n_propsets,
                   const mte_prop* props, uint32_t n_props) {
-  (void)n_props;
   if (!c || (n_docs && !docs)) return MTE_E_INVALID_ARG;
   free_docs(c);
-  c->arena_n = 0;
+  c->arena.n = 0;
   uint64_t base = 0;
-  int rc = arena_append(c, text, text_units, &base);
+  int rc = orc_arena_append(&c->arena, text, text_units, &base);
   if (rc) return rc;
-  c->docs = (odoc*)aligned_alloc(128, (size_t)(n_docs ? n_docs : 1) * sizeof(odoc));
-  if (c->docs) memset(c->docs, 0, (size_t)(n_docs ? n_docs : 1) * sizeof(odoc));
-  if (!c->docs) return MTE_E_OOM;
+  if (!(c->docs = (odoc*)orc_docs_alloc(n_docs, sizeof(odoc)))) return MTE_E_OOM;
   c->n_docs = n_docs;
-  c->load_units = text_units;
-  if (n_propsets) {
-    c->load_ps = (mte_propset*)malloc((size_t)n_propsets * sizeof(mte_propset));
-    if (!c->load_ps) return MTE_E_OOM;
-    memcpy(c->load_ps, propsets, (size_t)n_propsets * sizeof(mte_propset));
-    c->n_load_ps = n_propsets;
-  }
-  if (n_props) {
-    c->load_pe = (mte_prop*)malloc((size_t)n_props * sizeof(mte_prop));
-    if (!c->load_pe) return MTE_E_OOM;
-    memcpy(c->load_pe, props, (size_t)n_props * sizeof(mte_prop));
-    c->n_load_pe = n_props;
-  }
+  if ((rc = orc_load_tables_copy(&c->load, propsets, n_propsets, props, n_props, text_units))) return rc;
   for (uint32_t i = 0; i < n_docs; i++) {
     odoc* d = &c->docs[i];
     const mte_doc_init* in = &docs[i];
-    if ((uint64_t)in->text_off + in->text_len > text_units) return MTE_E_INVALID_ARG;
+    if ((rc = orc_init_text_check(in, text_units))) return rc;
     d->init = *in;
     d->flags = in->flags;
+    /* the flat rules restate a local client and events with the new length
+     * calculation only: the whole load is refused (chunked.c stops the one
+     * document; titems.c, the tree, replays it) */
     if ((in->flags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_EVENTS)) && !(in->flags & MTE_DOC_NEW_LENGTH_CALC))
       return MTE_E_UNSUPPORTED;
     if ((in->flags & MTE_DOC_REFS) && !(in->flags & MTE_DOC_LOCAL_CLIENT)) return MTE_E_UNSUPPORTED;
@@ -996,8 +962,7 @@ int orc_load_docs(orc_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
  * snapshotLoader.ts:85-125; IJSONSegmentWithMergeInfo, snapshotChunks.ts:48-78):
  * seq, clientId, removedSeq and removedClientIds are taken as given. */
 int orc_load_segments(orc_ctx* c, const uint64_t* seg_offsets, const mte_seg* segs, uint64_t n_segs) {
-  if (!c || !seg_offsets || (n_segs && !segs)) return MTE_E_INVALID_ARG;
-  if (seg_offsets[0] != 0 || seg_offsets[c->n_docs] != n_segs) return MTE_E_INVALID_ARG;
+  if (!c || orc_seg_offsets_check(seg_offsets, c->n_docs, segs, n_segs)) return MTE_E_INVALID_ARG;
   for (uint32_t i = 0; i < c->n_docs; i++) {
     const uint64_t b = seg_offsets[i], e = seg_offsets[i + 1];
     if (e < b) return MTE_E_INVALID_ARG;
@@ -1006,28 +971,17 @@ int orc_load_segments(orc_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
     int rc = doc_reserve(d, (uint32_t)(e - b) + 64);
     if (rc) return rc;
     for (uint64_t k = b; k < e; k++) {
-      const mte_seg* sg = &segs[k];
-      const int marker = sg->kind != 0;
-      if ((marker && sg->len != 1) || (!marker && (sg->len == 0 || (uint64_t)sg->text_off + sg->len > c->load_units)) ||
-          sg->client < -1 || sg->client >= MTE_MAX_CLIENTS || sg->seq < 0 ||
-          (sg->removed_seq != MTE_NOT_REMOVED && sg->removers == 0))
-        return MTE_E_INVALID_ARG;
+      orc_seg_fields f;
+      if ((rc = orc_seg_in(&segs[k], &c->load, &f))) return rc;
       oseg* g = &d->s[k - b];
       memset(g, 0, sizeof(*g));
       if (d->pk) memset(PK(d, k - b), 0, PKW * sizeof(uint32_t));
-      g->len = (int32_t)sg->len;
-      g->seq = sg->seq;
-      g->cli = sg->client;
-      g->rseq = sg->removed_seq == MTE_NOT_REMOVED ? NONE_SEQ : sg->removed_seq;
-      g->rmask = sg->removed_seq == MTE_NOT_REMOVED ? 0u : sg->removers;
-      g->kind = sg->kind;
-      /* a marker of an MTE_DOC_REFS document is named by its index in the load
-       * (above every arena offset), as an inserted one by its reserved unit */
-      g->toff = marker ? ((d->flags & MTE_DOC_REFS) ? 0x80000000u + (uint32_t)(k - b) : 0u) : sg->text_off;
-      if (sg->propset != MTE_NO_PROPS) {
-        if (sg->propset >= c->n_load_ps) return MTE_E_INVALID_ARG;
-        orc_apply_props(g->props, c->n_keys, &c->load_ps[sg->propset], c->load_pe, 0);
-      }
+      ORC_SEG_TAKE(g, f);
+      /* this restatement only: a marker of an MTE_DOC_REFS document is named by
+       * its index in the load (above every arena offset), as an inserted one by
+       * its reserved unit */
+      g->toff = (f.kind && (d->flags & MTE_DOC_REFS)) ? 0x80000000u + (uint32_t)(k - b) : f.toff;
+      orc_seg_in_props(&segs[k], &c->load, g->props, c->n_keys);
     }
     d->n = (uint32_t)(e - b);
   }
@@ -1038,8 +992,7 @@ typedef struct {
   orc_ctx* c;
   const mte_batch* b;
   uint64_t base;
-  uint32_t d0, d1, stride;
-} worker_arg;
+} batch_arg;
 
 /* MTE_DOC_ROUND_SYNC (include/mte.h) on a legacy-calc document: the batch's
  * live ops keep refSeq non-decreasing and each increase reaches every earlier
@@ -1062,198 +1015,90 @@ static int round_sync_ok(odoc* d, const mte_op* ops, uint64_t k0, uint64_t k1) {
   return 1;
 }
 
-static void* worker(void* p) {
-  worker_arg* w = (worker_arg*)p;
-  apply_env env = {w->b, w->base, w->c->n_keys, w->c->arena, NULL};
-  for (uint32_t di = w->d0; di < w->d1; di += w->stride) {
-    odoc* d = &w->c->docs[di];
-    if (d->status) continue;
-    if ((d->flags & (MTE_DOC_ROUND_SYNC | MTE_DOC_NEW_LENGTH_CALC)) == MTE_DOC_ROUND_SYNC &&
-        !round_sync_ok(d, w->b->ops, w->b->op_offsets[di], w->b->op_offsets[di + 1])) {
-      d->status = MTE_E_UNSUPPORTED;
-      continue;
-    }
-    d->dl_n = 0;
-    for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
-      const mte_op* op = &w->b->ops[k];
-      mte_op nx;
-      int rc = 0;
-      if (op->type == MTE_OP_RELPOS) {  /* the next record, at the resolved positions */
-        nx = op[1];
-        rc = doc_relpos(d, op, &nx, env.n_keys);
-        op = &nx;
-        k++;
-      }
-      d->cur_op = (uint32_t)(k - w->b->op_offsets[di]);
-      env.aux = &w->b->ops[k] + 1;
-      if (!rc) rc = doc_apply(d, op, &env);
-      if (rc) {
-        d->status = rc;
-        break;
-      }
-      if (op->type == MTE_OP_ROLLBACK && op->pos1 == MTE_OP_ANNOTATE) k += (uint64_t)op->pos2;  /* its RBKEY records */
-    }
+/* one document's records (titems.c's apply_doc is this loop's twin) */
+static void apply_doc(void* p, uint32_t di) {
+  const batch_arg* w = (const batch_arg*)p;
+  apply_env env = {w->b, w->base, w->c->n_keys, w->c->arena.p, NULL};
+  odoc* d = &w->c->docs[di];
+  if (d->status) return;
+  /* this restatement only: it alone takes round-synchronous legacy documents */
+  if ((d->flags & (MTE_DOC_ROUND_SYNC | MTE_DOC_NEW_LENGTH_CALC)) == MTE_DOC_ROUND_SYNC &&
+      !round_sync_ok(d, w->b->ops, w->b->op_offsets[di], w->b->op_offsets[di + 1])) {
+    d->status = MTE_E_UNSUPPORTED;
+    return;
   }
-  return NULL;
+  d->dl_n = 0;
+  for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
+    const mte_op* op = &w->b->ops[k];
+    mte_op nx;
+    int rc = 0;
+    if (op->type == MTE_OP_RELPOS) {  /* the next record, at the resolved positions */
+      nx = op[1];
+      rc = doc_relpos(d, op, &nx, env.n_keys);
+      op = &nx;
+      k++;
+    }
+    d->cur_op = (uint32_t)(k - w->b->op_offsets[di]);
+    env.aux = &w->b->ops[k] + 1;
+    if (!rc) rc = doc_apply(d, op, &env);
+    if (rc) {
+      d->status = rc;
+      break;
+    }
+    if (op->type == MTE_OP_ROLLBACK && op->pos1 == MTE_OP_ANNOTATE) k += (uint64_t)op->pos2;  /* its RBKEY records */
+  }
 }
 
 int orc_apply_batch(orc_ctx* c, const mte_batch* b, int n_threads) {
-  if (!c || !b || b->n_docs != c->n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
-  if (b->op_offsets[b->n_docs] != b->n_ops) return MTE_E_INVALID_ARG;
-  uint32_t dcur = 0;
-  uint64_t rbkey_end = 0;  /* records up to here are an annotate rollback's MTE_OP_RBKEY */
-  for (uint64_t k = 0; k < b->n_ops; k++) {
-    const mte_op* op = &b->ops[k];
-    while (dcur + 1 < b->n_docs && b->op_offsets[dcur + 1] <= k) dcur++;
-    /* local records (as mte_submit validates them) */
-    const int local_doc = (c->docs[dcur].flags & MTE_DOC_LOCAL_CLIENT) != 0;
-    if ((op->type == MTE_OP_RBKEY) != (k < rbkey_end)) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_ROLLBACK && op->pos1 == MTE_OP_ANNOTATE) {
-      if (op->pos2 < 0 || k + 1 + (uint64_t)op->pos2 > b->op_offsets[dcur + 1]) return MTE_E_INVALID_ARG;
-      rbkey_end = k + 1 + (uint64_t)op->pos2;
-    }
-    if (op->type > MTE_OP_RELPOS) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_RELPOS) {
-      const uint32_t rp = MTE_RP_POS1 | MTE_RP_BEFORE1 | MTE_RP_POS2 | MTE_RP_BEFORE2;
-      if ((op->flags & ~rp) || !(op->flags & (MTE_RP_POS1 | MTE_RP_POS2)) || k + 1 >= b->op_offsets[dcur + 1] ||
-          op[1].type > MTE_OP_ANNOTATE)
-        return MTE_E_INVALID_ARG;
-      continue;
-    }
-    if (op->type >= MTE_OP_ROLLBACK && !(op->flags & MTE_F_LOCAL)) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_REF) {
-      if (!(c->docs[dcur].flags & MTE_DOC_REFS) || op->seq != 0 || op->pos2 < 0 || op->b > 5 ||
-          op->client >= MTE_MAX_CLIENTS)
-        return MTE_E_INVALID_ARG;
-      continue;
-    }
-    if ((op->flags & MTE_F_LOCAL) && op->type == MTE_OP_ANNOTATE && op->b != MTE_NO_PROPS &&
-        op->b >= MTE_ANNOTATE_SLOTS)
-      return MTE_E_INVALID_ARG;
-    if ((op->flags & MTE_F_LOCAL) || op->type == MTE_OP_ACK) {
-      if (!local_doc) return MTE_E_INVALID_ARG;
-      if ((op->flags & MTE_F_LOCAL) && op->type != MTE_OP_RBKEY &&
-          (op->type == MTE_OP_ACK || op->seq <= 0 || op->seq >= MTE_LOCAL_SEQ_BASE))
-        return MTE_E_INVALID_ARG;
-      if (op->type == MTE_OP_RBKEY && (op->seq < 0 || op->seq >= MTE_LOCAL_SEQ_BASE || op->pos1 < 0 ||
-                                       op->pos1 >= MTE_MAX_KEYS || op->pos2 < 0 || op->pos2 > MTE_ANNOTATE_SLOTS))
-        return MTE_E_INVALID_ARG;
-      if (op->type == MTE_OP_ACK && (op->pos1 <= 0 || op->pos1 > op->pos2)) return MTE_E_INVALID_ARG;
-    }
-    if (local_doc && !(op->flags & MTE_F_LOCAL) && op->seq >= MTE_LOCAL_SEQ_BASE) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_INSERT && !(op->flags & MTE_F_MARKER) && op->pos2 > 0 &&
-        (uint64_t)op->a + (uint64_t)op->pos2 > b->text_units)
-      return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_INSERT && op->b != MTE_NO_PROPS && op->b >= b->n_propsets)
-      return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_ANNOTATE && op->a >= b->n_propsets) return MTE_E_INVALID_ARG;
-  }
-  uint64_t base = 0;
-  int rc = arena_append(c, b->text, b->text_units, &base);
+  if (!c) return MTE_E_INVALID_ARG;
+  /* local records too: this restatement replays local clients */
+  int rc = orc_check_batch(b, c->n_docs, c->docs ? &c->docs->flags : NULL, sizeof(odoc));
   if (rc) return rc;
+  batch_arg w = {c, b, 0};
+  if ((rc = orc_arena_append(&c->arena, b->text, b->text_units, &w.base))) return rc;
   /* stats describe the last batch, like mte_stats_get */
   for (uint32_t i = 0; i < c->n_docs; i++) {
     odoc* d = &c->docs[i];
     d->ops = d->scanned = d->written = d->pwrites = d->units = d->max_segs = 0;
   }
-  if (n_threads < 1) n_threads = 1;
-  if ((uint32_t)n_threads > c->n_docs) n_threads = c->n_docs ? (int)c->n_docs : 1;
-  worker_arg* args = (worker_arg*)calloc((size_t)n_threads, sizeof(worker_arg));
-  pthread_t* th = (pthread_t*)calloc((size_t)n_threads, sizeof(pthread_t));
-  if (!args || !th) {
-    free(args);
-    free(th);
-    return MTE_E_OOM;
-  }
-  for (int t = 0; t < n_threads; t++) {
-    args[t] = (worker_arg){c, b, base, (uint32_t)t, c->n_docs, (uint32_t)n_threads};
-  }
-  if (n_threads == 1) {
-    worker(&args[0]);
-  } else {
-    for (int t = 0; t < n_threads; t++) pthread_create(&th[t], NULL, worker, &args[t]);
-    for (int t = 0; t < n_threads; t++) pthread_join(th[t], NULL);
-  }
-  free(args);
-  free(th);
-  return MTE_OK;
+  return orc_run_docs(n_threads, c->n_docs, apply_doc, &w);
 }
 
 int orc_read_doc(orc_ctx* c, uint32_t doc, mte_doc_view* v) {
   if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
-  odoc* d = &c->docs[doc];
-  v->status = d->status;
-  v->cur_seq = d->cur_seq;
-  v->min_seq = d->min_seq;
-  uint32_t length = 0, nt = 0, ns = 0;
+  const odoc* d = &c->docs[doc];
+  orc_view_begin(v, d->status, d->cur_seq, d->min_seq);
   for (uint32_t i = 0; i < d->n; i++) {
     const oseg* g = &d->s[i];
     if (g->rseq != NONE_SEQ) continue; /* gatherText: removed -> not visible */
-    if (ns < v->seg_cap) {
-      if (v->seg_len) v->seg_len[ns] = (uint32_t)g->len;
-      if (v->seg_kind) v->seg_kind[ns] = g->kind;
-      if (v->seg_props)
-        for (uint32_t k = 0; k < c->n_keys; k++) v->seg_props[(size_t)ns * c->n_keys + k] = g->props[k];
-    }
-    ns++;
-    length += (uint32_t)g->len;
-    if (g->kind == 0) {
-      for (int32_t u = 0; u < g->len; u++) {
-        if (nt < v->text_cap && v->text) v->text[nt] = c->arena[g->toff + (uint32_t)u];
-        nt++;
-      }
-    }
+    orc_view_seg(v, c->n_keys, g->kind, g->len, g->props, g->kind == 0 ? c->arena.p + g->toff : NULL, 0);
   }
-  v->length = length;
-  v->n_text = nt;
-  v->n_segs = ns;
   return MTE_OK;
 }
 
 int orc_read_segments(orc_ctx* c, uint32_t doc, mte_seg_list* v) {
   if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
-  odoc* d = &c->docs[doc];
-  uint64_t nt = 0;
+  const odoc* d = &c->docs[doc];
+  orc_segs_begin(v);
   for (uint32_t i = 0; i < d->n; i++) {
     const oseg* g = &d->s[i];
-    if (i < v->seg_cap && v->segs) {
-      mte_seg* s = &v->segs[i];
-      s->text_off = g->kind == 0 ? (uint32_t)nt : 0u;
-      s->len = (uint32_t)g->len;
-      s->seq = g->seq;
-      s->removed_seq = g->rseq == NONE_SEQ ? MTE_NOT_REMOVED : g->rseq;
-      s->removers = g->rseq == NONE_SEQ ? 0u : g->rmask;
-      s->client = g->cli;
-      s->kind = g->kind;
-      s->propset = MTE_NO_PROPS;
-      if (v->props)
-        for (uint32_t k = 0; k < c->n_keys; k++) v->props[(size_t)i * c->n_keys + k] = g->props[k];
-    }
-    if (g->kind == 0)
-      for (int32_t u = 0; u < g->len; u++, nt++)
-        if (nt < v->text_cap && v->text) v->text[nt] = c->arena[g->toff + (uint32_t)u];
+    orc_segs_seg(v, c->n_keys, ORC_SEG_GIVE(g), g->props, g->kind == 0 ? c->arena.p + g->toff : NULL, 0);
   }
-  v->n_segs = d->n;
-  v->n_text = nt;
   return MTE_OK;
 }
 
-/* ---- canonical digest (DESIGN.md "Digest", orc_common.h) ------------------ */
+/* ---- canonical digest (DESIGN.md "Digest", orc_shell.h) ------------------- */
 int orc_digest(orc_ctx* c, uint64_t* out, uint32_t n_docs) {
   if (!c || !out || n_docs != c->n_docs) return MTE_E_INVALID_ARG;
   for (uint32_t di = 0; di < n_docs; di++) {
-    odoc* d = &c->docs[di];
+    const odoc* d = &c->docs[di];
     orc_digest_acc acc = {0, 0, 0, 0};
     for (uint32_t i = 0; i < d->n; i++) {
       const oseg* g = &d->s[i];
       if (g->rseq != NONE_SEQ) continue;
-      orc_digest_seg(&acc, g->kind, g->kind == 0 ? c->arena + g->toff : NULL, g->len, g->props, c->n_keys);
+      orc_digest_seg(&acc, g->kind, g->kind == 0 ? c->arena.p + g->toff : NULL, g->len, g->props, c->n_keys);
     }
-    const uint64_t n = acc.n, h1 = acc.h1, h2 = acc.h2, sum = acc.sum;
-    out[4 * (size_t)di + 0] = n;
-    out[4 * (size_t)di + 1] = h1;
-    out[4 * (size_t)di + 2] = h2;
-    out[4 * (size_t)di + 3] = sum;
+    orc_digest_out(out, di, &acc);
   }
   return MTE_OK;
 }
@@ -1268,17 +1113,10 @@ int orc_stats_get(orc_ctx* c, mte_stats* o) {
   if (!c || !o) return MTE_E_INVALID_ARG;
   memset(o, 0, sizeof(*o));
   for (uint32_t i = 0; i < c->n_docs; i++) {
-    odoc* d = &c->docs[i];
-    o->ops_applied += d->ops;
-    o->segs_scanned += d->scanned;
-    o->segs_written += d->written;
-    o->prop_writes += d->pwrites;
-    o->units_inserted += d->units;
-    if (d->max_segs > o->max_segs) o->max_segs = d->max_segs;
+    const odoc* d = &c->docs[i];
+    orc_stats_add(o, d->ops, d->scanned, d->written, d->pwrites, d->units, d->max_segs);
   }
-  o->algo_bytes = 32.0 * (double)o->ops_applied + 20.0 * (double)o->segs_scanned +
-                  20.0 * (double)o->segs_written + 4.0 * (double)o->prop_writes +
-                  2.0 * (double)o->units_inserted;
+  orc_stats_end(o);
   return MTE_OK;
 }
 
@@ -1290,9 +1128,7 @@ int orc_doc_nsegs(orc_ctx* c, uint32_t doc, uint32_t* out) {
 
 int orc_read_deltas(orc_ctx* c, uint32_t doc, mte_delta* out, uint64_t cap, uint64_t* n) {
   if (!c || !n || doc >= c->n_docs) return MTE_E_INVALID_ARG;
-  const odoc* d = &c->docs[doc];
-  *n = d->dl_n;
-  if (out) memcpy(out, d->dl, (size_t)(cap < d->dl_n ? cap : d->dl_n) * sizeof(mte_delta));
+  orc_deltas_out(c->docs[doc].dl, c->docs[doc].dl_n, out, cap, n);
   return MTE_OK;
 }
 

@@ -25,14 +25,16 @@
  * caches: partialLengths.ts:667-702 == the leaf sum, test/testUtils.ts:173-248).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg load it.
+ *
+ * The replay rules end at the API banner below; under it is glue over the shell
+ * the four restatements share (orc_shell.h: arena, load tables, load and batch
+ * validation, thread pool, read-out emitters).  What this file does differently
+ * from the other three stands there once, at its call site, with a comment.
  */
 #include <limits.h>
-#include <pthread.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include "orc_common.h"
+#include "orc_shell.h"
 #include "tree.h"
 
 #define NONE_SEQ ORC_NONE_SEQ
@@ -84,12 +86,8 @@ struct ort_ctx {
   uint32_t n_keys;
   uint32_t n_docs;
   tdoc* docs;
-  uint16_t* load_text;
-  uint64_t load_units;
-  mte_propset* load_ps;
-  uint32_t n_load_ps;
-  mte_prop* load_pe;
-  uint32_t n_load_pe;
+  uint16_t* load_text; /* text lives on the leaves: no arena, the load text alone is kept */
+  orc_load_tables load;
 };
 
 /* ---- nodes ---------------------------------------------------------------- */
@@ -712,13 +710,8 @@ static void free_docs(ort_ctx* c) {
   c->docs = NULL;
   c->n_docs = 0;
   free(c->load_text);
-  free(c->load_ps);
-  free(c->load_pe);
   c->load_text = NULL;
-  c->load_ps = NULL;
-  c->load_pe = NULL;
-  c->load_units = 0;
-  c->n_load_ps = c->n_load_pe = 0;
+  orc_load_tables_free(&c->load);
 }
 
 int ort_destroy(ort_ctx* c) {
@@ -733,30 +726,17 @@ int ort_load_docs(ort_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
                   const mte_prop* props, uint32_t n_props) {
   if (!c || (n_docs && !docs)) return MTE_E_INVALID_ARG;
   free_docs(c);
-  c->docs = (tdoc*)aligned_alloc(128, (size_t)(n_docs ? n_docs : 1) * sizeof(tdoc));
-  if (!c->docs) return MTE_E_OOM;
-  memset(c->docs, 0, (size_t)(n_docs ? n_docs : 1) * sizeof(tdoc));
+  if (!(c->docs = (tdoc*)orc_docs_alloc(n_docs, sizeof(tdoc)))) return MTE_E_OOM;
   c->n_docs = n_docs;
   c->load_text = (uint16_t*)malloc((size_t)(text_units ? text_units : 1) * sizeof(uint16_t));
   if (!c->load_text) return MTE_E_OOM;
   if (text_units) memcpy(c->load_text, text, (size_t)text_units * sizeof(uint16_t));
-  c->load_units = text_units;
-  if (n_propsets) {
-    c->load_ps = (mte_propset*)malloc((size_t)n_propsets * sizeof(mte_propset));
-    if (!c->load_ps) return MTE_E_OOM;
-    memcpy(c->load_ps, propsets, (size_t)n_propsets * sizeof(mte_propset));
-    c->n_load_ps = n_propsets;
-  }
-  if (n_props) {
-    c->load_pe = (mte_prop*)malloc((size_t)n_props * sizeof(mte_prop));
-    if (!c->load_pe) return MTE_E_OOM;
-    memcpy(c->load_pe, props, (size_t)n_props * sizeof(mte_prop));
-    c->n_load_pe = n_props;
-  }
+  int rc = orc_load_tables_copy(&c->load, propsets, n_propsets, props, n_props, text_units);
+  if (rc) return rc;
   for (uint32_t i = 0; i < n_docs; i++) {
     tdoc* d = &c->docs[i];
     const mte_doc_init* in = &docs[i];
-    if ((uint64_t)in->text_off + in->text_len > text_units) return MTE_E_INVALID_ARG;
+    if ((rc = orc_init_text_check(in, text_units))) return rc;
     d->init = *in;
     d->flags = in->flags;
     d->min_seq = in->min_seq;
@@ -764,6 +744,7 @@ int ort_load_docs(ort_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
     d->root = make_block(); /* MergeTree constructor: an empty root (mergeTree.ts:495-498) */
     if (!d->root) return MTE_E_OOM;
     if (in->text_len > 0) {
+      if (in->propset != MTE_NO_PROPS && in->propset >= n_propsets) return MTE_E_INVALID_ARG; /* before the leaf: no leak */
       /* the harness's insertTextLocal before collaboration
        * (client.replay.spec.ts:22-23): one seq-0 LocalClientId leaf */
       tnode* g = make_leaf();
@@ -775,7 +756,6 @@ int ort_load_docs(ort_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
       if (!g->text) return MTE_E_OOM;
       memcpy(g->text, text + in->text_off, (size_t)in->text_len * sizeof(uint16_t));
       if (in->propset != MTE_NO_PROPS) {
-        if (in->propset >= n_propsets) return MTE_E_INVALID_ARG;
         g->po = 1;
         orc_apply_props(g->props, c->n_keys, &propsets[in->propset], props, 0);
       }
@@ -815,8 +795,7 @@ static tnode* build_level(tnode** nodes, uint32_t n, int* oom) {
 }
 
 int ort_load_segments(ort_ctx* c, const uint64_t* seg_offsets, const mte_seg* segs, uint64_t n_segs) {
-  if (!c || !seg_offsets || (n_segs && !segs)) return MTE_E_INVALID_ARG;
-  if (seg_offsets[0] != 0 || seg_offsets[c->n_docs] != n_segs) return MTE_E_INVALID_ARG;
+  if (!c || orc_seg_offsets_check(seg_offsets, c->n_docs, segs, n_segs)) return MTE_E_INVALID_ARG;
   for (uint32_t i = 0; i < c->n_docs; i++) {
     const uint64_t b = seg_offsets[i], e = seg_offsets[i + 1];
     if (e < b) return MTE_E_INVALID_ARG;
@@ -826,32 +805,21 @@ int ort_load_segments(ort_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
     if (!leaves) return MTE_E_OOM;
     for (uint64_t k = b; k < e; k++) {
       const mte_seg* sg = &segs[k];
-      const int marker = sg->kind != 0;
-      if ((marker && sg->len != 1) || (!marker && (sg->len == 0 || (uint64_t)sg->text_off + sg->len > c->load_units)) ||
-          sg->client < -1 || sg->client >= MTE_MAX_CLIENTS || sg->seq < 0 ||
-          (sg->removed_seq != MTE_NOT_REMOVED && sg->removers == 0)) {
+      orc_seg_fields f;
+      if (orc_seg_in(sg, &c->load, &f)) {
         for (uint64_t q = b; q < k; q++) free_leaf(leaves[q - b]);
         free(leaves);
         return MTE_E_INVALID_ARG;
       }
       tnode* g = make_leaf();
       if (!g) return MTE_E_OOM;
-      g->len = (int32_t)sg->len;
-      g->seq = sg->seq;
-      g->cli = sg->client;
-      g->rseq = sg->removed_seq == MTE_NOT_REMOVED ? NONE_SEQ : sg->removed_seq;
-      g->rmask = sg->removed_seq == MTE_NOT_REMOVED ? 0u : sg->removers;
-      g->kind = sg->kind;
-      if (!marker) {
+      ORC_SEG_TAKE(g, f);
+      if (!f.kind) {  /* this restatement only: each leaf owns its text */
         g->text = (uint16_t*)malloc((size_t)sg->len * sizeof(uint16_t));
         if (!g->text) return MTE_E_OOM;
-        memcpy(g->text, c->load_text + sg->text_off, (size_t)sg->len * sizeof(uint16_t));
+        memcpy(g->text, c->load_text + f.toff, (size_t)sg->len * sizeof(uint16_t));
       }
-      if (sg->propset != MTE_NO_PROPS) {
-        if (sg->propset >= c->n_load_ps) return MTE_E_INVALID_ARG;
-        g->po = 1;
-        orc_apply_props(g->props, c->n_keys, &c->load_ps[sg->propset], c->load_pe, 0);
-      }
+      g->po = orc_seg_in_props(sg, &c->load, g->props, c->n_keys);
       leaves[k - b] = g;
     }
     int oom = 0;
@@ -867,93 +835,50 @@ int ort_load_segments(ort_ctx* c, const uint64_t* seg_offsets, const mte_seg* se
 typedef struct {
   ort_ctx* c;
   const mte_batch* b;
-  uint32_t d0, d1, stride;
-} worker_arg;
+} batch_arg;
 
-static void* worker(void* p) {
-  worker_arg* w = (worker_arg*)p;
+/* one document's records: remote ones only, no MTE_OP_RELPOS stepping */
+static void apply_doc(void* p, uint32_t di) {
+  const batch_arg* w = (const batch_arg*)p;
   apply_env env = {w->b, w->b->text, w->c->n_keys};
-  for (uint32_t di = w->d0; di < w->d1; di += w->stride) {
-    tdoc* d = &w->c->docs[di];
-    if (d->status) continue;
-    for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
-      int rc = doc_apply(d, &w->b->ops[k], &env);
-      if (rc) {
-        d->status = rc;
-        break;
-      }
+  tdoc* d = &w->c->docs[di];
+  if (d->status) return;
+  for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
+    int rc = doc_apply(d, &w->b->ops[k], &env);
+    if (rc) {
+      d->status = rc;
+      break;
     }
   }
-  return NULL;
 }
 
 int ort_apply_batch(ort_ctx* c, const mte_batch* b, int n_threads) {
-  if (!c || !b || b->n_docs != c->n_docs || !b->op_offsets) return MTE_E_INVALID_ARG;
-  if (b->op_offsets[b->n_docs] != b->n_ops) return MTE_E_INVALID_ARG;
-  for (uint64_t k = 0; k < b->n_ops; k++) {
-    const mte_op* op = &b->ops[k];
-    if (op->type == MTE_OP_INSERT && !(op->flags & MTE_F_MARKER) && op->pos2 > 0 &&
-        (uint64_t)op->a + (uint64_t)op->pos2 > b->text_units)
-      return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_INSERT && op->b != MTE_NO_PROPS && op->b >= b->n_propsets) return MTE_E_INVALID_ARG;
-    if (op->type == MTE_OP_ANNOTATE && op->a >= b->n_propsets) return MTE_E_INVALID_ARG;
-  }
+  if (!c) return MTE_E_INVALID_ARG;
+  /* no document flags: a record this restatement does not replay (local, ack,
+   * reference, relative position) stops its document in doc_apply */
+  int rc = orc_check_batch(b, c->n_docs, NULL, 0);
+  if (rc) return rc;
+  /* the structure counters describe the last batch (ort_stats_get) */
   for (uint32_t i = 0; i < c->n_docs; i++) {
     tdoc* d = &c->docs[i];
     d->ops = d->n_push = d->n_pop = d->n_scour = d->n_split = d->n_pack = d->n_merge = 0;
   }
-  if (n_threads < 1) n_threads = 1;
-  if ((uint32_t)n_threads > c->n_docs) n_threads = c->n_docs ? (int)c->n_docs : 1;
-  worker_arg* args = (worker_arg*)calloc((size_t)n_threads, sizeof(worker_arg));
-  pthread_t* th = (pthread_t*)calloc((size_t)n_threads, sizeof(pthread_t));
-  if (!args || !th) {
-    free(args);
-    free(th);
-    return MTE_E_OOM;
-  }
-  for (int t = 0; t < n_threads; t++) args[t] = (worker_arg){c, b, (uint32_t)t, c->n_docs, (uint32_t)n_threads};
-  if (n_threads == 1) {
-    worker(&args[0]);
-  } else {
-    for (int t = 0; t < n_threads; t++) pthread_create(&th[t], NULL, worker, &args[t]);
-    for (int t = 0; t < n_threads; t++) pthread_join(th[t], NULL);
-  }
-  free(args);
-  free(th);
-  return MTE_OK;
+  batch_arg w = {c, b};
+  return orc_run_docs(n_threads, c->n_docs, apply_doc, &w);
 }
 
 int ort_read_doc(ort_ctx* c, uint32_t doc, mte_doc_view* v) {
   if (!c || !v || doc >= c->n_docs) return MTE_E_INVALID_ARG;
   tdoc* d = &c->docs[doc];
-  v->status = d->status;
-  v->cur_seq = d->cur_seq;
-  v->min_seq = d->min_seq;
   uint32_t n = 0;
   int rc = flatten(d, &n);
   if (rc) return rc;
-  uint32_t length = 0, nt = 0, ns = 0;
+  orc_view_begin(v, d->status, d->cur_seq, d->min_seq);
   for (uint32_t i = 0; i < n; i++) {
     const tnode* g = d->flat[i];
     if (g->rseq != NONE_SEQ) continue; /* gatherText: removed -> not visible */
-    if (ns < v->seg_cap) {
-      if (v->seg_len) v->seg_len[ns] = (uint32_t)g->len;
-      if (v->seg_kind) v->seg_kind[ns] = g->kind;
-      if (v->seg_props)
-        for (uint32_t k = 0; k < c->n_keys; k++) v->seg_props[(size_t)ns * c->n_keys + k] = g->props[k];
-    }
-    ns++;
-    length += (uint32_t)g->len;
-    if (g->kind == 0) {
-      for (int32_t u = 0; u < g->len; u++) {
-        if (nt < v->text_cap && v->text) v->text[nt] = g->text[u];
-        nt++;
-      }
-    }
+    orc_view_seg(v, c->n_keys, g->kind, g->len, g->props, g->text, 0);
   }
-  v->length = length;
-  v->n_text = nt;
-  v->n_segs = ns;
   return MTE_OK;
 }
 
@@ -963,28 +888,11 @@ int ort_read_segments(ort_ctx* c, uint32_t doc, mte_seg_list* v) {
   uint32_t n = 0;
   int rc = flatten(d, &n);
   if (rc) return rc;
-  uint64_t nt = 0;
+  orc_segs_begin(v);
   for (uint32_t i = 0; i < n; i++) {
     const tnode* g = d->flat[i];
-    if (i < v->seg_cap && v->segs) {
-      mte_seg* s = &v->segs[i];
-      s->text_off = g->kind == 0 ? (uint32_t)nt : 0u;
-      s->len = (uint32_t)g->len;
-      s->seq = g->seq;
-      s->removed_seq = g->rseq == NONE_SEQ ? MTE_NOT_REMOVED : g->rseq;
-      s->removers = g->rseq == NONE_SEQ ? 0u : g->rmask;
-      s->client = g->cli;
-      s->kind = g->kind;
-      s->propset = MTE_NO_PROPS;
-      if (v->props)
-        for (uint32_t k = 0; k < c->n_keys; k++) v->props[(size_t)i * c->n_keys + k] = g->props[k];
-    }
-    if (g->kind == 0)
-      for (int32_t u = 0; u < g->len; u++, nt++)
-        if (nt < v->text_cap && v->text) v->text[nt] = g->text[u];
+    orc_segs_seg(v, c->n_keys, ORC_SEG_GIVE(g), g->props, g->text, 0);
   }
-  v->n_segs = n;
-  v->n_text = nt;
   return MTE_OK;
 }
 
@@ -1001,10 +909,7 @@ int ort_digest(ort_ctx* c, uint64_t* out, uint32_t n_docs) {
       if (g->rseq != NONE_SEQ) continue;
       orc_digest_seg(&acc, g->kind, g->text, g->len, g->props, c->n_keys);
     }
-    out[4 * (size_t)di + 0] = acc.n;
-    out[4 * (size_t)di + 1] = acc.h1;
-    out[4 * (size_t)di + 2] = acc.h2;
-    out[4 * (size_t)di + 3] = acc.sum;
+    orc_digest_out(out, di, &acc);
   }
   return MTE_OK;
 }
