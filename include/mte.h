@@ -273,6 +273,17 @@ extern "C" {
 
 #define MTE_F_MARKER 0x0001u  /* insert spec {marker:{refType}} (mergeTreeNodes.ts:602-609) */
 #define MTE_F_MSG_END 0x0002u /* last record of its message: window update follows      */
+/* A batch may end inside a message: the records of one message (same seq,
+ * MTE_F_MSG_END on the last only) may be split over two mte_submit calls at
+ * any record.  The document's window (currentSeq, minSeq) moves only at the
+ * record that carries MTE_F_MSG_END, in whichever batch it arrives, and the
+ * two batches leave the document as the one batch does -- on the flat passes
+ * (new length-calc and MTE_DOC_ROUND_SYNC documents) at every document size.
+ * One limitation, on the HBM tree pass only: the positions of a message's
+ * MTE_DELTA_MAINT records (MTE_DOC_MAINT_EVENTS) are filled in when the
+ * record with MTE_F_MSG_END has been applied, within one batch; those of a
+ * message still open at the end of a batch are left unresolved, so a host
+ * that reads maintenance events ends its batches at message ends.           */
 #define MTE_F_REWRITE 0x0004u /* annotate combiningOp {name:"rewrite"} (segmentPropertiesManager.ts:105-119) */
 /* A sequenced annotate with combiningOp "incr" or "consensus": the reference
  * sets each key to combine(op, currentValue, undefined, seq)

@@ -1020,6 +1020,11 @@ static void apply_doc(void* p, uint32_t di) {
   const batch_arg* w = (const batch_arg*)p;
   apply_env env = {w->b, w->base, w->c->n_keys, w->c->arena.p, NULL};
   odoc* d = &w->c->docs[di];
+  /* the events are the last batch's (include/mte.h mte_read_deltas): a stopped
+   * document applies no record of this one, so no delta callback fires
+   * (mergeTree.ts:1409-1416) and it has none, as the engine clears every
+   * document's count at mte_submit */
+  d->dl_n = 0;
   if (d->status) return;
   /* this restatement only: it alone takes round-synchronous legacy documents */
   if ((d->flags & (MTE_DOC_ROUND_SYNC | MTE_DOC_NEW_LENGTH_CALC)) == MTE_DOC_ROUND_SYNC &&
@@ -1027,7 +1032,6 @@ static void apply_doc(void* p, uint32_t di) {
     d->status = MTE_E_UNSUPPORTED;
     return;
   }
-  d->dl_n = 0;
   for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
     const mte_op* op = &w->b->ops[k];
     mte_op nx;

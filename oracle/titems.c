@@ -1936,8 +1936,8 @@ static void apply_doc(void* p, uint32_t di) {
   const batch_arg* w = (const batch_arg*)p;
   env_t env = {w->b, w->base, w->c->n_keys, w->c->arena.p, w->c->limit, NULL};
   idoc* d = &w->c->docs[di];
+  d->dl_n = 0; /* a stopped document too has no events in this batch (oracle.c apply_doc) */
   if (d->status) return;
-  d->dl_n = 0;
   for (uint64_t k = w->b->op_offsets[di]; k < w->b->op_offsets[di + 1]; k++) {
     const mte_op* op = &w->b->ops[k];
     mte_op nx;

@@ -292,10 +292,10 @@ LAYOUT_CASES = {
 
 # ---- capacity -----------------------------------------------------------------
 
-def nsegs_trace(stream):
+def nsegs_trace(stream, before=()):
     """-> int64[n_docs, max ops + 1]: the segments each document holds before
     its op i (column i) in the flat restatement, tombstones included; after its
-    last op the count repeats."""
+    last op the count repeats.  before: batches applied ahead of the traced one."""
     from fluidframework_amd import gen
     from oracle import OracleEngine
     b = stream["batch"]
@@ -304,6 +304,8 @@ def nsegs_trace(stream):
     nd, steps = len(cnt), int(cnt.max()) if len(cnt) else 0
     o = OracleEngine(stream["n_keys"], threads=1)
     gen.load_stream(o, stream)
+    for earlier in before:
+        o.apply_batch(earlier)
     out = np.zeros((nd, steps + 1), np.int64)
     out[:, 0] = [o.nsegs(d) for d in range(nd)]
     for i in range(steps):

@@ -75,6 +75,7 @@ def prop_sets(layout):
         "M_twice": [(MID, mid + 4), (B, 37), (MID, mid + 5)],
         "M_none": [(B, 38), (COL, 48)],
         "M_deleted": [(MID, mid + 6), (COL, 41), (MID, 0)],
+        "E_0": [],  # no entries (tests/big_doc_cases.py); last, so the sets above keep their numbers
     }
     names = list(sets)
     return [sets[k] for k in names], {k: i for i, k in enumerate(names)}
@@ -342,10 +343,11 @@ def all_cases():
 GROUPS = ("edge", "window", "prec", "advance", "tier", "props")
 
 
-def build_stream(cases, layout, pad_to=0, cut=None):
+def build_stream(cases, layout, pad_to=0, cut=None, n_keys=se.N_KEYS):
     """-> (stream, batches): the cases as documents 0 .. len(cases) - 1, then
     trivial documents up to pad_to.  cut(d) -> (batch, records): document d's
-    records up to there only."""
+    records up to there only.  A case may carry its own document flags
+    (`flags`) and more or fewer than two batches (tests/big_doc_cases.py)."""
     ns = [d.n for d in cases] + [1] * max(0, pad_to - len(cases))
     nd = len(ns)
     units = SEG * np.array(ns, np.int64)
@@ -353,6 +355,7 @@ def build_stream(cases, layout, pad_to=0, cut=None):
     inits = np.zeros(nd, DOC_INIT_DTYPE)
     inits["text_off"], inits["text_len"] = text_off[:-1], units
     inits["flags"], inits["propset"] = DOC_NEW_LENGTH_CALC, NO_PROPS
+    inits["flags"][:len(cases)] = [getattr(d, "flags", DOC_NEW_LENGTH_CALC) for d in cases]
     inits["min_seq"], inits["cur_seq"] = MIN0, CUR0
     init_text = (65 + np.arange(int(text_off[-1])) % 26).astype(np.uint16)
     seg_offs = np.concatenate([[0], np.cumsum(ns)]).astype(np.uint64)
@@ -370,10 +373,10 @@ def build_stream(cases, layout, pad_to=0, cut=None):
     pe = np.array([e for x in sets for e in x], PROP_DTYPE)
     text = (97 + np.arange(TEXT_UNITS) % 26).astype(np.uint16)
     batches = []
-    for bi in range(2):
+    for bi in range(max(len(d.batches) for d in cases)):
         recs = []
         for i, d in enumerate(cases):
-            r = d.batches[bi]
+            r = d.batches[bi] if bi < len(d.batches) else []
             if cut is not None:
                 cb, ck = cut(d)
                 r = r if bi < cb else (r[:ck] if bi == cb else [])
@@ -385,7 +388,7 @@ def build_stream(cases, layout, pad_to=0, cut=None):
         ops = np.array(flat, OP_DTYPE) if flat else np.zeros(0, OP_DTYPE)
         offs = np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.uint64)
         batches.append({"op_offsets": offs, "ops": ops, "text": text, "propsets": ps, "props": pe})
-    stream = {"inits": inits, "init_text": init_text, "n_keys": se.N_KEYS, "segs": (seg_offs, segs), "batch": batches[0]}
+    stream = {"inits": inits, "init_text": init_text, "n_keys": n_keys, "segs": (seg_offs, segs), "batch": batches[0]}
     return stream, batches
 
 

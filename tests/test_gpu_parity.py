@@ -153,8 +153,9 @@ def replay_both_cap(stream, cap, threads=8):
     return o, d
 
 
-def test_gpu_stream_pass_insert_heavy_large_docs():
-    # insert-only docs grow past the register tiers (1,022 segments): pass 3
+def test_gpu_chunk_pass_insert_heavy_large_docs():
+    # insert-only docs grow past the register tiers (1,022 segments): pass 3,
+    # which is chunk_kernel in a context of 8,192 segments and more (launch_replay)
     # (new length calc; legacy documents live in the tree pass, <= 1,020 items)
     s = gen.generate(2, n_docs=12, ops_per_doc=2600, mix=gen.MIX_INSERT, min_length=0, length_mode=2)
     o, d = replay_both_cap(s, 8192)
@@ -163,9 +164,10 @@ def test_gpu_stream_pass_insert_heavy_large_docs():
     assert_same(o, d, sample_docs=12)
 
 
-def test_gpu_stream_pass_long_docs_all_ops():
+def test_gpu_chunk_pass_long_docs_all_ops():
     # config-5 shaped (scaled down): a long initial text split by insert /
-    # remove / annotate ops in deep rounds (1,024 concurrent ops)
+    # remove / annotate ops in deep rounds (1,024 concurrent ops); a 16,384-segment
+    # context: the chunked pass (statistics on: op after op)
     s = gen.generate(3, n_docs=6, ops_per_doc=4000, init_len=20000, round_ops=1024, min_length=16,
                      length_mode=2)
     o, d = replay_both_cap(s, 16384)
@@ -196,7 +198,8 @@ def test_gpu_tree_pass_capacity_is_the_context_capacity():
     assert_same(o, d, sample_docs=4)
 
 
-def test_gpu_stream_pass_annotate_heavy():
+def test_gpu_chunk_pass_annotate_heavy():
+    # a 16,384-segment context: the chunked pass
     s = gen.generate(3, n_docs=6, ops_per_doc=3000, init_len=6000, round_ops=512, min_length=16,
                      length_mode=2, mix=gen.MIX_INSERT | gen.MIX_ANNOTATE)
     o, d = replay_both_cap(s, 16384)
@@ -206,6 +209,7 @@ def test_gpu_stream_pass_annotate_heavy():
 
 
 def test_gpu_stream_pass_capacity_error():
+    # 1,536 segments: below kChunkMinCap, pass 3 is stream_kernel
     s = gen.generate(2, n_docs=3, ops_per_doc=1400, mix=gen.MIX_INSERT, min_length=0)
     o, d = replay_both_cap(s, 1536)
     assert o.stats()["max_segs"] > 1534
