@@ -118,6 +118,22 @@ POS_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4")])
 assert POS_QUERY_DTYPE.itemsize == 8
 POS_HIT_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("kind", "<u4"), ("reserved", "<u4")])
 assert POS_HIT_DTYPE.itemsize == 16
+# mte_read_ref_positions: a query and its answer's header
+REFS_TRANSIENT = 0x1
+REF_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("first", "<u4"), ("count", "<u4"), ("flags", "<u4")])
+assert REF_QUERY_DTYPE.itemsize == 16
+REF_INFO_DTYPE = np.dtype([("status", "<i4"), ("cur_seq", "<i4"), ("min_seq", "<i4"), ("length", "<u4"),
+                           ("offset", "<u8")])
+assert REF_INFO_DTYPE.itemsize == 24
+
+
+class MteRefQuery(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MteRefInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("cur_seq", C.c_int32), ("min_seq", C.c_int32), ("length", C.c_uint32),
+                ("offset", C.c_uint64)]
 
 
 class MteTextQuery(C.Structure):
@@ -181,7 +197,7 @@ EXPORTED_SYMBOLS = [
     "mte_comm_unique_id", "mte_comm_init", "mte_comm_share", "mte_comm_barrier", "mte_comm_allreduce_f64",
     "mte_comm_gather_digests", "mte_comm_world", "mte_comm_destroy", "mte_read_deltas", "mte_set_event_capacity",
     "mte_set_ref_capacity", "mte_read_refs", "mte_read_refs_transient", "mte_read_ref_order", "mte_find_tiles",
-    "mte_read_texts", "mte_props_at",
+    "mte_read_texts", "mte_props_at", "mte_read_ref_positions",
 ]
 
 DOC_EVENTS = 0x8

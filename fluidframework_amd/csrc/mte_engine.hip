@@ -719,6 +719,9 @@ struct mte_ctx {
   // mte_read_texts: the queries (2 words each) then their offsets; the infos (4 words each); the units
   DevBuf<uint64_t> text_in, text_info;
   DevBuf<uint16_t> text_out;
+  // mte_read_ref_positions: the queries (2 words each) then the tasks (2 words each);
+  // the infos (3 words each), the order keys, the positions (two a word)
+  DevBuf<uint64_t> ref_in, ref_out;
   // per key, the largest property value id the context was given (load +
   // every batch) and whether any text segment or annotate ever carried it:
   // pass 1 packs the 4 property planes into one (kPack4) when every key's ids
@@ -1343,6 +1346,7 @@ int mte_destroy(mte_ctx* c) {
   free_buf(c->d_comm);
   free_buf(c->tile_in), free_buf(c->tile_out);
   free_buf(c->text_in), free_buf(c->text_info), free_buf(c->text_out);
+  free_buf(c->ref_in), free_buf(c->ref_out);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->tree_stream) (void)hipStreamDestroy(c->tree_stream);
@@ -2310,6 +2314,68 @@ int mte_props_at(mte_ctx* c, const mte_pos_query* q, uint32_t n, mte_pos_hit* ou
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(out, res.data(), hw * 4);
   if (pw) std::memcpy(out_props, res.data() + hw, pw * 4);
+  return MTE_OK;
+}
+
+int mte_read_ref_positions(mte_ctx* c, const mte_ref_query* q, uint32_t n, mte_ref_info* info, int32_t* pos,
+                           int64_t* order, uint64_t cap) {
+  if (!c || (n && (!q || !info))) return MTE_E_INVALID_ARG;
+  uint64_t total = 0, n_tasks = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const mte_ref_query& t = q[i];
+    if (t.doc >= c->docs.n_docs || !(c->docs.flags[t.doc] & MTE_DOC_REFS) || (uint64_t)t.first + t.count > c->ref_cap ||
+        (t.flags & ~MTE_REFS_TRANSIENT))
+      return set_err(c, MTE_E_INVALID_ARG,
+                     "mte_read_ref_positions: query %u (doc %u%s, slots [%u, +%u) of %u, flags 0x%x)", i, t.doc,
+                     t.doc < c->docs.n_docs && !(c->docs.flags[t.doc] & MTE_DOC_REFS) ? ": no MTE_DOC_REFS" : "", t.first,
+                     t.count, c->ref_cap, t.flags);
+    total += t.count;
+    if (total > cap)
+      return set_err(c, MTE_E_INVALID_ARG, "mte_read_ref_positions: query %u: %llu slots up to it, cap %llu", i,
+                     (unsigned long long)total, (unsigned long long)cap);
+    n_tasks += t.count ? (t.count + 63u) / 64u : 1u;  // a query without slots still answers info
+  }
+  if (n_tasks >= (1ull << 32)) return set_err(c, MTE_E_INVALID_ARG, "mte_read_ref_positions: too many slots for one call");
+  JOIN_TAIL(c);
+  if (!n) return MTE_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  static_assert(sizeof(mte_ref_query) == 16 && sizeof(mte_ref_info) == 24, "mte_read_ref_positions packs these as 64-bit words");
+  // one upload (queries, then one task per 64 slots), one launch, one download (infos, keys, positions)
+  const uint64_t qw = 2ull * n, iw = 3ull * n, ow = order ? total : 0, pw = pos ? (total + 1) / 2 : 0;
+  std::vector<uint64_t> in(qw + 2 * n_tasks), res(iw + ow + pw);
+  std::memcpy(in.data(), q, 16ull * n);
+  uint32_t* tk = reinterpret_cast<uint32_t*>(in.data() + qw);
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t nb = q[i].count ? (q[i].count + 63u) / 64u : 1u;
+    for (uint32_t b = 0; b < nb; b++, tk += 4) {
+      const uint64_t o = off + 64ull * b;
+      tk[0] = i, tk[1] = b, tk[2] = (uint32_t)o, tk[3] = (uint32_t)(o >> 32);
+    }
+    off += q[i].count;
+  }
+  if (int rc = grow(c, c->ref_in, in.size())) return rc;
+  if (int rc = grow(c, c->ref_out, res.size())) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->ref_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+  RefArgs a;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
+  a.cap = c->cap;
+  a.tree = c->docs.d_tree;  // null without tree documents: the kernel reads it only for a doc_has_tree document
+  a.refs = c->docs.d_refs;
+  a.ref_cap = c->ref_cap;
+  a.n_tasks = (uint32_t)n_tasks;
+  a.q = (const mte_ref_query*)c->ref_in.p;
+  a.tasks = (const uint4*)(c->ref_in.p + qw);
+  a.info = (mte_ref_info*)c->ref_out.p;
+  a.order = order ? (int64_t*)(c->ref_out.p + iw) : nullptr;
+  a.pos = pos ? (int32_t*)(c->ref_out.p + iw + ow) : nullptr;
+  HIPCHK(c, launch_ref_positions(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res.data(), c->ref_out.p, res.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(info, res.data(), iw * 8);
+  if (order && total) std::memcpy(order, res.data() + iw, total * 8);
+  if (pos && total) std::memcpy(pos, res.data() + iw + ow, total * 4);
   return MTE_OK;
 }
 

@@ -237,4 +237,21 @@ struct PosArgs {
 };
 hipError_t launch_props_at(const PosArgs& a, hipStream_t s);
 
+// mte_read_ref_positions: one wave per task = (query, block of 64 slots)
+struct RefArgs {
+  const DocHdr* hdr;
+  SegSoA soa;
+  uint32_t cap;
+  const uint32_t* tree;        // the tree words; null in a context without tree documents
+  const uint2* refs;
+  uint32_t ref_cap;
+  uint32_t n_tasks;
+  const mte_ref_query* q;      // validated by the host (doc, MTE_DOC_REFS, first + count, flags)
+  const uint4* tasks;          // x query | y slot block | z, w where the block's answers start (64 bits)
+  mte_ref_info* info;          // [queries], written by each query's block 0
+  int32_t* pos;                // or null
+  int64_t* order;              // or null
+};
+hipError_t launch_ref_positions(const RefArgs& a, hipStream_t s);
+
 }  // namespace mte

@@ -43,6 +43,34 @@
 // correct, slow for a document of a million segments; no tile-parallel variant
 // is built.  The four waves of a workgroup walk different documents: nothing
 // block-wide sits in any loop.
+//
+// ref_positions_kernel answers mte_read_ref_positions: read_refs_view and
+// mte_read_ref_order (mte_engine.hip) for any number of documents, both views
+// and the order key from one walk.  One wave takes one (query, block of 64
+// reference slots): lane r holds slot first + 64 b + r of the document's
+// reference table.  The wave walks the document 64 segments a step as
+// props_at_kernel does (len, rseq, toff coalesced; the tree word only where the
+// block holds a Transient slot; one scan for the visible lengths, one for all
+// lengths when the order is asked for), then broadcasts the step's segments one
+// after the other with v_readlane at a uniform index (toff and len; the leaf
+// id and the head bit, a ballot, only where the block holds a Transient slot)
+// while every lane still looking tests its own reference and keeps the index of
+// the first segment in document order that holds its unit.  After the step each
+// lane pulls that segment's prefixes and removed flag across the wave
+// (ds_bpermute), so the inner loop carries two broadcasts and a compare.  The
+// wave leaves the walk when a ballot shows no lane looking; the wave of slot
+// block 0 walks on without the inner loop, for getLength.
+//
+// The (query, block) of a wave comes from a task table the host uploads with
+// the queries (16 B a wave: query, block, where the block's answers start),
+// rather than from a search of a block-prefix array: the host sums the counts
+// anyway for the offsets, the table is at most a quarter of the answers it
+// describes, and a wave starts with one load where the search would take
+// log2(n) dependent ones before its first useful load.
+// 256 threads, no LDS (the pulls use the crossbar only), 24 VGPRs and no scratch
+// as the gfx950 -O3 build reports.  One wave walks a whole document per
+// 64 slots: correct, slow for a document of a million segments; no
+// tile-parallel variant is built.
 #pragma once
 
 #include "mte_kernels.h"
@@ -257,6 +285,107 @@ __global__ __launch_bounds__(256) void props_at_kernel(PosArgs a) {
   if (a.out_props && (uint32_t)l < a.n_keys)
     a.out_props[(uint64_t)qi * a.n_keys + l] =
         hit_slot >= 0 ? a.soa.props[(uint64_t)l * a.soa.plane_stride + db + hit_slot] : 0u;
+}
+
+__global__ __launch_bounds__(256) void ref_positions_kernel(RefArgs a) {
+  const int w = threadIdx.x / kWave;
+  const int l = lane_id();
+  const uint32_t ti = blockIdx.x * kQueriesPerBlock + (uint32_t)w;
+  if (ti >= a.n_tasks) return;
+  const uint4 t = a.tasks[ti];
+  const uint32_t qi = uni(t.x), blk = uni(t.y);
+  const uint64_t out0 = uni64((uint64_t)t.z | ((uint64_t)t.w << 32));
+  const mte_ref_query q = a.q[qi];
+  const uint32_t doc = uni(q.doc), count = uni(q.count);
+  const bool transient = (uni(q.flags) & MTE_REFS_TRANSIENT) != 0;
+  const DocHdr h = a.hdr[doc];
+  int n = h.status == MTE_OK ? h.nseg : 0;  // a stopped document answers -1 (and length 0)
+  n = n < 0 ? 0 : (n > (int)a.cap ? (int)a.cap : n);
+  const uint64_t db = (uint64_t)doc * a.cap;
+  const bool want_pos = a.pos != nullptr, want_order = a.order != nullptr;
+
+  const uint32_t s = blk * (uint32_t)kWave + (uint32_t)l;  // < count <= ref_cap - first
+  const bool mine = s < count;
+  const uint2 rt = mine ? a.refs[(uint64_t)doc * a.ref_cap + uni(q.first) + s] : make_uint2(0u, 0u);
+  const bool live = (rt.y & kRefLive) != 0;
+  const bool trans = live && (rt.y & kRefTrans);
+  // what the lane still looks for (want): bit 0 the segment holding its unit,
+  // for the position (up), the order key (uo) or both; bit 1 its Transient
+  // slot's leaf
+  const bool up = want_pos && live && !trans && !((rt.y & kRefDetached) && !(transient && (rt.y & kRefOff)));
+  const bool uo = want_order && live && !((rt.y & kRefDetached) && !(rt.y & kRefOff));
+  uint32_t want = ((up || uo) ? 1u : 0u) | ((want_pos && trans) ? 2u : 0u);
+  const bool any_trans = __ballot(want & 2u) != 0;
+  // the tree words, for the leaf ids: zeros for a document without them, as the host reads them
+  const bool tree = doc_has_tree(h.flags) && any_trans;
+  const bool lead = blk == 0;  // this wave also answers info, so it walks to the end
+
+  int32_t pos = -1, carry = 0;
+  int64_t key = -1, ocarry = 0;
+  for (int c0 = 0; c0 < n; c0 += kWave) {
+    const bool look = __ballot(want != 0) != 0;
+    if (!look && !lead) break;
+    const int i = c0 + l;
+    const bool in = i < n;
+    const int32_t rs = in ? a.soa.rseq[db + i] : kNone;
+    const int32_t L = in ? a.soa.len[db + i] : 0;
+    const int32_t V = rs == kNone ? L : 0;
+    const int32_t vincl = wave_incl_scan(V);
+    if (look) {
+      const uint32_t to = in ? a.soa.toff[db + i] : 0u;
+      const uint32_t tw = (in && tree) ? a.tree[db + i] : 0u;
+      const int32_t P = carry + vincl - V;
+      const int32_t O = want_order ? wave_incl_scan(L) - L : 0;  // below 2^31: the units are distinct arena units
+      const unsigned long long head = __ballot(!(tw & (kTCont | kTEmpty)));
+      const uint32_t id = (tw >> 8) & (kIdLimit - 1u);
+      const int m = n - c0 < kWave ? n - c0 : kWave;
+      // the step's segments, broadcast in document order: the first that holds
+      // the lane's unit (ju), the head of its leaf (jt)
+      int ju = -1, jt = -1;
+      for (int j = 0; j < m; j++) {
+        if (__ballot(want != 0) == 0) break;
+        const uint32_t d = rt.x - rdlane(to, j);
+        const bool hu = ((want & 1u) != 0) & (d < (uint32_t)rdlane(L, j));  // & not &&: no branch round a compare
+        ju = hu ? j : ju;
+        want = hu ? want & ~1u : want;
+        if (any_trans) {
+          const bool ht = ((want & 2u) != 0) & (((head >> j) & 1ull) != 0) & (rdlane(id, j) == rt.x);
+          jt = ht ? j : jt;
+          want = ht ? want & ~2u : want;
+        }
+      }
+      // each lane pulls its segment's words (every lane takes part in the pull)
+      const int pu = (ju < 0 ? 0 : ju) << 2;
+      const uint32_t d = rt.x - (uint32_t)__builtin_amdgcn_ds_bpermute(pu, (int32_t)to);
+      const int32_t Pu = __builtin_amdgcn_ds_bpermute(pu, P);
+      const bool gone_u = __builtin_amdgcn_ds_bpermute(pu, rs) != kNone;
+      if (ju >= 0 && up) pos = Pu + (gone_u ? 0 : (int32_t)d);
+      if (want_order) {
+        const int32_t Ou = __builtin_amdgcn_ds_bpermute(pu, O);
+        if (ju >= 0 && uo) key = ocarry + (int64_t)Ou + (int64_t)d;
+        ocarry += (int64_t)rdlane(O + L, kWave - 1);
+      }
+      if (any_trans) {
+        const int pt = (jt < 0 ? 0 : jt) << 2;
+        const int32_t Pt = __builtin_amdgcn_ds_bpermute(pt, P);
+        const bool gone_t = __builtin_amdgcn_ds_bpermute(pt, rs) != kNone;
+        if (jt >= 0) pos = Pt + (gone_t ? 0 : (int32_t)(rt.y & kRefTransOff));
+      }
+    }
+    carry += rdlane(vincl, kWave - 1);
+  }
+  if (mine) {
+    if (want_pos) a.pos[out0 + l] = pos;
+    if (want_order) a.order[out0 + l] = key;
+  }
+  if (lead && l == 0) {
+    mte_ref_info* o = a.info + qi;
+    o->status = h.status;
+    o->cur_seq = h.cur_seq;
+    o->min_seq = h.min_seq;
+    o->length = (uint32_t)carry;
+    o->offset = out0;
+  }
 }
 
 }  // namespace mte

@@ -27,4 +27,9 @@ hipError_t launch_props_at(const PosArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_ref_positions(const RefArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(ref_positions_kernel, dim3(query_blocks(a.n_tasks)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace mte

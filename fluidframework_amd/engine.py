@@ -11,7 +11,8 @@ import numpy as np
 
 from . import _native
 from .abi import (DELTA_DTYPE, DOC_INIT_DTYPE, EXPORTED_SYMBOLS, OP_DTYPE, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE,
-                  POS_HIT_DTYPE, POS_QUERY_DTYPE, TEXT_INFO_DTYPE, TEXT_PLACEHOLDERS, TEXT_QUERY_DTYPE, TEXT_TO_END,
+                  POS_HIT_DTYPE, POS_QUERY_DTYPE, REF_INFO_DTYPE, REF_QUERY_DTYPE, REFS_TRANSIENT,
+                  TEXT_INFO_DTYPE, TEXT_PLACEHOLDERS, TEXT_QUERY_DTYPE, TEXT_TO_END,
                   TILE_HIT_DTYPE, TILE_PRECEDING, TILE_QUERY_DTYPE,
                   MergeTreeError, MteBatch, MteConfig, MteDocView, MteSegList, MteStats, ptr)
 from .packing import units_to_str
@@ -100,6 +101,20 @@ class EngineBase:
         out = np.zeros(max(n, 1), np.int64)
         self._check(self.lib.mte_read_ref_order(self.ctx, doc, ptr(out), n), "read_ref_order")
         return out[:n]
+
+    def read_ref_positions(self, queries, order=False):
+        """Reference positions for many documents at once: queries = [(doc,
+        first, count, transient)] -> [int32[count]] (read_refs' answers for slots
+        [first, first + count), read_refs(transient=True)'s with transient set),
+        and with order=True also [int64[count]] (read_ref_order's keys).  Here
+        through the per-document calls; DeviceEngine answers all of them by one
+        device call (include/mte.h mte_read_ref_positions)."""
+        pos, keys = [], []
+        for doc, first, count, transient in queries:
+            pos.append(self.read_refs(doc, first + count, transient=bool(transient))[first:].copy())
+            if order:
+                keys.append(self.read_ref_order(doc, first + count)[first:].copy())
+        return (pos, keys) if order else pos
 
     def read_segments(self, doc):
         """-> (segs SEG_DTYPE[n] with text_off into text, props uint32[n, n_keys], text uint16[])."""
@@ -344,6 +359,37 @@ class DeviceEngine(EngineBase):
                 raise MergeTreeError(int(h["status"]), f"props_at: document {int(q[i]['doc'])}")
             out.append(interner.decode_props(props[i]) if h["found"] else None)
         return out
+
+    def read_ref_positions_raw(self, q, want_pos=True, want_order=False):
+        """mte_read_ref_positions over REF_QUERY_DTYPE[n] -> (REF_INFO_DTYPE[n],
+        int32[sum of counts] or None, int64[sum of counts] or None): query i's
+        slots at info["offset"][i] .. + its count, from one device call."""
+        q = _arr(q, REF_QUERY_DTYPE)
+        info = np.zeros(len(q), REF_INFO_DTYPE)
+        total = int(q["count"].astype(np.uint64).sum())
+        pos = np.zeros(max(total, 1), np.int32) if want_pos else None
+        keys = np.zeros(max(total, 1), np.int64) if want_order else None
+        self._check(self.lib.mte_read_ref_positions(self.ctx, ptr(q), len(q), ptr(info), ptr(pos), ptr(keys), total),
+                    "read_ref_positions")
+        return info, None if pos is None else pos[:total], None if keys is None else keys[:total]
+
+    def read_ref_positions(self, queries, order=False):
+        """EngineBase.read_ref_positions by one device call for all queries
+        (include/mte.h mte_read_ref_positions).  Raises MergeTreeError for a
+        document whose status is not OK.  One wavefront walks a queried document
+        per 64 slots: slow for a document of a million segments."""
+        q = np.zeros(len(queries), REF_QUERY_DTYPE)
+        for i, (doc, first, count, transient) in enumerate(queries):
+            q[i] = (doc, first, count, REFS_TRANSIENT if transient else 0)
+        info, pos, keys = self.read_ref_positions_raw(q, want_order=order)
+        for i, h in enumerate(info):
+            if h["status"] != 0:
+                raise MergeTreeError(int(h["status"]), f"read_ref_positions: document {int(q[i]['doc'])}")
+        cuts = np.cumsum(q["count"].astype(np.int64))[:-1]
+        out = [a.copy() for a in np.split(pos, cuts)] if len(q) else []
+        if not order:
+            return out
+        return out, ([a.copy() for a in np.split(keys, cuts)] if len(q) else [])
 
     def _read_doc(self, doc, vptr):
         return self.lib.mte_read_doc(self.ctx, doc, vptr)

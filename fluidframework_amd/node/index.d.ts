@@ -197,6 +197,14 @@ export class MergeTreeEngine {
    *  device call (mte_props_at) for the whole array; undefined where the
    *  segment has no properties or pos is at or past the length. */
   getPropertiesAt(queries: PositionQuery[]): (PropertySet | undefined)[];
+  /** Local reference positions of many documents: one flush, one sync and one
+   *  device call (mte_read_ref_positions) for every given client's reference
+   *  slots (every client with {refs: true} when none is given).  The answers
+   *  fill the per-flush caches behind localReferencePositionToPosition, the
+   *  interval collections and their tree order, which then make no device
+   *  call until the next flush.  transient: also as Transient references;
+   *  order: also the document-order keys. */
+  prefetchRefs(clients?: BatchClient[] | null, options?: { transient?: boolean; order?: boolean }): void;
   digests(): BigUint64Array;
   statuses(): Int32Array;
   stats(): EngineStats;

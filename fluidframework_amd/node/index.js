@@ -437,6 +437,52 @@ class MergeTreeEngine {
     return out;
   }
 
+  /** Read the local reference positions of many documents at once
+   *  (mte_read_ref_positions): one flush, one sync and one device call for
+   *  slots [0, refNext) of every given client -- of every client with local
+   *  references ({refs: true}) when none is given.  The answers fill the
+   *  per-flush caches localReferencePositionToPosition, the interval
+   *  collections and the order reads consult, so those make no further device
+   *  call until the next flush.  options.transient also reads the positions as
+   *  Transient references (a changeInterval event's previous interval),
+   *  options.order the document-order keys.  A document whose status is not OK
+   *  is left to the per-document reads.  One wavefront walks each document per
+   *  64 slots: slow over a document of a million segments.
+   *  @param {BatchClient[]} [clients]
+   *  @param {{transient?: boolean, order?: boolean}} [options] */
+  prefetchRefs(clients, options) {
+    this.flush();
+    this.sync();
+    const o = options || {};
+    const docs = [];
+    if (clients === undefined || clients === null) {
+      this.docs.forEach((d, i) => { if (d.refs) docs.push(i); });
+    } else {
+      clients.forEach((c, i) => {
+        const doc = this._queryDoc("prefetchRefs", i, { client: c });
+        if (!this.docs[doc].refs) throw new MergeTreeError(-1, "prefetchRefs: client " + i + " has no local references");
+        docs.push(doc);
+      });
+    }
+    const per = o.transient ? 2 : 1;
+    const q = new Uint32Array(4 * per * docs.length);
+    docs.forEach((doc, i) => {
+      const n = this.clients[doc].clients.refNext;
+      q.set([doc, 0, n, 0], 4 * per * i);
+      if (o.transient) q.set([doc, 0, n, 1], 4 * per * i + 4);
+    });
+    if (docs.length === 0) return;
+    const r = this.addon.readRefPositions(this.ctx, q, !!o.order);
+    docs.forEach((doc, i) => {
+      const at = (k) => r.info[6 * (per * i + k) + 4] + r.info[6 * (per * i + k) + 5] * 4294967296;
+      if ((r.info[6 * per * i] | 0) !== 0) return;
+      const n = q[4 * per * i + 2];
+      this.refViews[doc] = r.pos.slice(at(0), at(0) + n);
+      if (o.transient) this.refViewsT[doc] = r.pos.slice(at(1), at(1) + n);
+      if (o.order) this.orderViews[doc] = r.order.slice(at(0), at(0) + n);
+    });
+  }
+
   /** Per-doc canonical digests (4 x u64 each, DESIGN.md "Digest"). */
   digests() {
     this.flush();

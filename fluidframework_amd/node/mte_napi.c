@@ -799,6 +799,62 @@ static napi_value js_props_at(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* readRefPositions(ctx, queries, wantOrder) -> {info Uint32Array(6n)
+   (mte_ref_info: status, curSeq, minSeq, length, offset low, offset high), pos
+   Int32Array(total), order Float64Array(total) with wantOrder}:
+   mte_read_ref_positions over queries = Uint32Array(4n) (mte_ref_query: doc,
+   first, count, flags), total = the sum of the counts.  Weak, as
+   mte_find_tiles is. */
+extern __typeof__(mte_read_ref_positions) mte_read_ref_positions __attribute__((weak));
+
+static napi_value js_read_ref_positions(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return NULL;
+  ctx_box* box = get_box(env, argv[0]);
+  if (!box) return NULL;
+  void* q = NULL;
+  size_t qb = 0;
+  bool want_order = false;
+  if (!get_bytes(env, argv[1], &q, &qb)) return NULL;
+  if (napi_get_value_bool(env, argv[2], &want_order) != napi_ok) want_order = false;
+  if (!mte_read_ref_positions) {
+    throw_rc(env, MTE_E_UNSUPPORTED, NULL, "readRefPositions: this engine library has no mte_read_ref_positions");
+    return NULL;
+  }
+  if (qb % sizeof(mte_ref_query) || qb / sizeof(mte_ref_query) > 0xffffffffu) {
+    throw_rc(env, MTE_E_INVALID_ARG, box->ctx, "readRefPositions: buffer size");
+    return NULL;
+  }
+  const size_t n = qb / sizeof(mte_ref_query);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) total += ((const mte_ref_query*)q)[i].count;
+  napi_value o, ab_i, ab_p, ab_o, ti, tp, to;
+  void *pi = NULL, *pp = NULL, *po = NULL;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(mte_ref_info), &pi, &ab_i));
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)total * 4, &pp, &ab_p));
+  if (want_order) NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)total * 8, &po, &ab_o));
+  if (throw_rc(env, mte_read_ref_positions(box->ctx, (const mte_ref_query*)q, (uint32_t)n, (mte_ref_info*)pi,
+                                           (int32_t*)pp, want_order ? (int64_t*)po : NULL, total),
+               box->ctx, "mte_read_ref_positions"))
+    return NULL;
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n * 6, ab_i, 0, &ti));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, (size_t)total, ab_p, 0, &tp));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "info", ti);
+  napi_set_named_property(env, o, "pos", tp);
+  if (want_order) { /* the keys as doubles, in place: readRefOrder's form */
+    for (uint64_t i = 0; i < total; i++) {
+      int64_t k;
+      memcpy(&k, (const char*)po + 8 * i, 8);
+      const double v = (double)k;
+      memcpy((char*)po + 8 * i, &v, 8);
+    }
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, (size_t)total, ab_o, 0, &to));
+    napi_set_named_property(env, o, "order", to);
+  }
+  return o;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   const napi_property_descriptor d[] = {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -834,6 +890,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"findTiles", NULL, js_find_tiles, NULL, NULL, NULL, napi_default, NULL},
       {"readTexts", NULL, js_read_texts, NULL, NULL, NULL, napi_default, NULL},
       {"propsAt", NULL, js_props_at, NULL, NULL, NULL, napi_default, NULL},
+      {"readRefPositions", NULL, js_read_ref_positions, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

@@ -736,6 +736,38 @@ typedef struct mte_pos_query { uint32_t doc; int32_t pos; } mte_pos_query;
 typedef struct mte_pos_hit   { int32_t status; int32_t found; uint32_t kind; uint32_t reserved; } mte_pos_hit;
 int mte_props_at(mte_ctx* ctx, const mte_pos_query* q, uint32_t n, mte_pos_hit* out, uint32_t* out_props);
 
+/* ---- Batched local-reference read-out: positions for many documents --------
+ * mte_read_refs, mte_read_refs_transient and mte_read_ref_order for any number
+ * of MTE_DOC_REFS documents in one device call.  Query i asks for reference
+ * slots [first, first + count) of `doc`; its answers start at info[i].offset in
+ * `pos` and `order`, the exclusive prefix sum of the counts in query order (the
+ * caller can compute it: there is no size-then-fill round).  `cap` is what
+ * `pos` / `order` hold, in slots, and must be >= the sum of the counts.
+ *
+ * pos (may be NULL): per slot exactly what mte_read_refs returns, or with
+ * MTE_REFS_TRANSIENT on the query what mte_read_refs_transient returns.
+ * order (may be NULL): per slot exactly mte_read_ref_order's key.  Either, or
+ * both from the same call.  info[i] holds the document's status, collab window
+ * and getLength().  A document whose status is not MTE_OK answers -1 for every
+ * slot (and length 0), with its status.  Queries may name documents in any
+ * order, with repeats; count == 0 is allowed; n == 0 launches nothing.
+ *
+ * MTE_E_INVALID_ARG, before any launch and with the outputs untouched
+ * (mte_last_error names the query), for a null context, doc >= n_docs, a
+ * document without MTE_DOC_REFS, first + count > the reference capacity
+ * (mte_set_ref_capacity), an unknown flag or cap below the sum of the counts.
+ * The device work is one upload (the queries and one 16-byte task per 64
+ * slots), one kernel launch, one download and one synchronisation, whatever n
+ * and the number of documents.  One wavefront walks a whole document per 64
+ * slots, so a document of a million segments is slow (no tile-parallel variant
+ * exists yet).  Which segment holds a reference is not returned.             */
+#define MTE_REFS_TRANSIENT 0x1u            /* read as mte_read_refs_transient does */
+typedef struct mte_ref_query { uint32_t doc, first, count, flags; } mte_ref_query;      /* 16 B */
+typedef struct mte_ref_info  { int32_t status, cur_seq, min_seq; uint32_t length;
+                               uint64_t offset; } mte_ref_info;                          /* 24 B */
+int mte_read_ref_positions(mte_ctx* ctx, const mte_ref_query* q, uint32_t n, mte_ref_info* info,
+                           int32_t* pos, int64_t* order, uint64_t cap);
+
 int mte_doc_status(mte_ctx* ctx, int32_t* out, uint32_t n_docs);
 int mte_stats_get(mte_ctx* ctx, mte_stats* out);
 /* Statistics accounting (the counters of mte_stats, like the reference's
