@@ -18,6 +18,7 @@
 
 #include "mte_kernels.h"
 #include "mte_passes.h"
+#include "pool_layout.h"
 
 #include <rccl/rccl.h>
 
@@ -619,7 +620,7 @@ struct DocState {
   uint64_t* d_digest = nullptr;
   SegImage image;
   // diagnostics: MTE_WAVE_CLOCK=<file> dumps pass-1 start / end times per
-  // pair (s_memrealtime, 100 MHz) at every mte_sync
+  // wave (s_memrealtime, 100 MHz) at every mte_sync
   unsigned long long* d_wclock = nullptr;
   // chunked big-document pass (seg_capacity >= kChunkMinCap, mte_chunk.h) and
   // its round phases (mte_round.h)
@@ -629,9 +630,16 @@ struct DocState {
   // tile-parallel digest of big-document contexts (dg_*_kernel), allocated at
   // the first digest of such a context
   DigestTiles dgt{};
-  uint32_t* d_pairs = nullptr;  // pass-1 doc pairs (new length calc documents)
-  uint32_t n_pairs = 0;         // pass-1 waves
-  uint32_t pass1_group = 1;     // documents per pass-1 wave
+  // pass-1 pools of the flat documents (pool_layout.h; the table as
+  // ReplayArgs::pools wants it), laid out once for each waves-per-SIMD figure
+  // an instantiation of pass 1 may be built for: which one runs is known at
+  // the launch (pass1_packs, mte_set_stats)
+  struct Pools {
+    uint32_t* d = nullptr;
+    uint32_t n = 0;    // pools = pass-1 workgroups
+    uint32_t max = 0;  // documents in the largest
+  } pools[kPass1WavesMax - kPass1WavesMin + 1];
+  uint32_t pool_waves = 0;  // waves of the larger table (sizes d_wclock)
   // tree pass (legacy length calc documents, mte_tree.h)
   uint32_t* d_tree = nullptr;       // tree word per slot
   uint2* d_heap = nullptr;          // LRU heap per document
@@ -987,20 +995,29 @@ int launch_replay(mte_ctx* c, const ReplayArgs& a) {
     }
     HIPCHK(c, hipEventRecord(c->ev_join, c->tree_stream));
   }
-  // pass 1: two documents per wavefront (docs up to 126 segments)
-  const uint32_t b1 = (c->docs.n_pairs + kPairsPerBlock - 1) / kPairsPerBlock;
-  // with 4 keys whose value ids all fit in a byte (every value the context was
+  // pass 1: one workgroup per pool of flat documents (docs up to 254
+  // segments), the pools laid out for the instantiation's waves per SIMD.
+  // With 4 keys whose value ids all fit in a byte (every value the context was
   // ever given), pass 1 holds the four planes as one packed register plane
-  if (b1) {
-    if constexpr (K == 4) {
-      uint32_t side;
-      const bool pack = pass1_packs(c, &side);
-      ReplayArgs ap = a;
-      ap.side_key = side;
-      if (pack) HIPCHK(c, (launch_pair<kPack4, S>(ap, b1, c->stream)));
-      else HIPCHK(c, (launch_pair<K, S>(a, b1, c->stream)));
-    } else {
-      HIPCHK(c, (launch_pair<K, S>(a, b1, c->stream)));
+  {
+    uint32_t side = kNoKey;
+    const bool pack = K == 4 && pass1_packs(c, &side);
+    const DocState::Pools& pl = c->docs.pools[pass1_waves(pack ? kPack4 : K, S) - kPass1WavesMin];
+    ReplayArgs ap = a;
+    ap.pools = pl.d;
+    ap.n_pools = pl.n;
+    ap.pool_max = pl.max;
+    if (pl.n) {
+      if constexpr (K == 4) {
+        if (pack) {
+          ap.side_key = side;
+          HIPCHK(c, (launch_pair<kPack4, S>(ap, pl.n, c->stream)));
+        } else {
+          HIPCHK(c, (launch_pair<K, S>(ap, pl.n, c->stream)));
+        }
+      } else {
+        HIPCHK(c, (launch_pair<K, S>(ap, pl.n, c->stream)));
+      }
     }
   }
   // pass 2: docs that outgrew pass 1 continue one per wavefront (up to 1022 segments)
@@ -1500,21 +1517,25 @@ int mte_load_docs(mte_ctx* c, uint32_t n_docs, const mte_doc_init* docs, const u
     MTECHK(doc_upload(c, &ds.d_init_props, iprops));
     MTECHK(doc_alloc(c, &ds.d_digest, 4ull * n_docs));
     {
-      // pass-1 groups: g consecutive documents per wave, g the smallest count
-      // that puts the whole batch on the chip at once (CUs x 4 SIMDs x
-      // pass1_waves() waves), so a batch that fits at one document per wave
-      // (config 2's 1k docs, the 1,250 per GPU of an 8-GPU 10k job) runs one per
-      // wave: grouping it would leave SIMDs idle and serialise its documents.
+      // pass-1 pools (pool_layout.h): a batch that fits the chip at one document
+      // per wave (config 2's 1k docs, the 1,250 per GPU of an 8-GPU 10k job)
+      // runs one per wave; a larger one gets a pool per resident workgroup,
+      // whose waves share the pool's documents, so the whole batch is on the
+      // chip at once with every wave slot filled
       const uint32_t nf = (uint32_t)flat_docs.size();
       int n_cu = 0;
       if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) n_cu = 0;
-      const uint64_t resident = (n_cu > 0 ? (uint64_t)n_cu : 256) * 4 * (uint64_t)pass1_waves();
-      const uint32_t g = (uint32_t)std::min<uint64_t>(kGroupMax, std::max<uint64_t>(1, (nf + resident - 1) / resident));
-      ds.pass1_group = g;
-      ds.n_pairs = (nf + g - 1) / g;
-      std::vector<uint32_t> pairs((size_t)ds.n_pairs * g + g, 0xffffffffu);
-      std::copy(flat_docs.begin(), flat_docs.end(), pairs.begin());
-      MTECHK(doc_upload(c, &ds.d_pairs, pairs));
+      ds.pool_waves = 0;
+      for (int w = kPass1WavesMin; w <= kPass1WavesMax; w++) {
+        const PoolLayout L = pool_layout(nf, n_cu > 0 ? (uint32_t)n_cu : 256u, (uint32_t)w, kPairsPerBlock, kPoolMax);
+        DocState::Pools& pl = ds.pools[w - kPass1WavesMin];
+        pl.n = L.n_pools;
+        pl.max = L.pool_max;
+        std::vector<uint32_t> tab(L.first);
+        tab.insert(tab.end(), flat_docs.begin(), flat_docs.end());
+        MTECHK(doc_upload(c, &pl.d, tab));
+        ds.pool_waves = std::max(ds.pool_waves, pl.n * (uint32_t)kPairsPerBlock);
+      }
     }
     ds.n_rs = (uint32_t)rs_docs.size();
     if (ds.n_rs) MTECHK(doc_upload(c, &ds.d_rs_docs, rs_docs));
@@ -1820,9 +1841,9 @@ int mte_run(mte_ctx* c) {
   a.n_keys = c->n_keys;
   a.text_base = s.text_base;
   a.stats = c->docs.stats;
-  a.pair_docs = c->docs.d_pairs;
-  a.n_pairs = c->docs.n_pairs;
-  a.group = c->docs.pass1_group;
+  a.pools = nullptr;  // launch_replay picks the table of the instantiation it launches
+  a.n_pools = 0;
+  a.pool_max = 0;
   a.wclock = nullptr;
   const bool evs = !s.h_dl_off.empty();  // some document of the batch records events
   a.dl = evs ? s.dl.p : nullptr;
@@ -1844,12 +1865,14 @@ int mte_run(mte_ctx* c) {
     eta_ms = c->last_ms * (double)s.n_ops / c->last_ops;
   } else if (s.n_ops) {
     const double thr = 2.15e-7 * (double)s.n_ops;
-    const double chain = 8.5e-4 * (double)s.max_doc_ops * (double)c->docs.pass1_group;
+    // documents per wave: the largest pool's over its workgroup's waves
+    const uint32_t per_wave = (c->docs.pools[0].max + kPairsPerBlock - 1) / kPairsPerBlock;
+    const double chain = 8.5e-4 * (double)s.max_doc_ops * (double)std::max(1u, per_wave);
     eta_ms = std::max(thr, chain);
   }
   a.eta = (unsigned long long)(eta_ms * 1e5);
   if (c->wclock_path) {
-    if (!c->docs.d_wclock) MTECHK(doc_alloc(c, &c->docs.d_wclock, 2ull * (c->docs.n_pairs + 1)));
+    if (!c->docs.d_wclock) MTECHK(doc_alloc(c, &c->docs.d_wclock, 2ull * (c->docs.pool_waves + 1), true));
     a.wclock = c->docs.d_wclock;
   }
   if (c->docs.n_rs) {
@@ -1904,7 +1927,7 @@ int mte_sync(mte_ctx* c) {
     }
   }
   if (c->wclock_path && c->docs.d_wclock) {
-    std::vector<unsigned long long> w(2ull * c->docs.n_pairs);
+    std::vector<unsigned long long> w(2ull * c->docs.pool_waves);
     HIPCHK(c, hipMemcpy(w.data(), c->docs.d_wclock, w.size() * 8, hipMemcpyDeviceToHost));
     if (FILE* f = std::fopen(c->wclock_path, "wb")) {
       std::fwrite(w.data(), 8, w.size(), f);

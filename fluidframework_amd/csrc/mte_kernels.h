@@ -24,7 +24,8 @@ constexpr int32_t kNone = INT32_MAX;  // removedSeq undefined (not removed)
 constexpr int32_t kPad = INT32_MIN;   // removedSeq of a padding slot
 constexpr int kDocsPerBlock = 4;      // big-doc kernel: 4 waves (docs) per workgroup
 constexpr int kPairsPerBlock = 4;     // pass-1 kernel: 4 waves per workgroup
-constexpr int kGroupMax = 8;          // pass 1: at most this many documents per wave
+constexpr int kGroupMax = 8;          // pass 1: at most this many documents per wave of a workgroup, so
+constexpr int kPoolMax = kPairsPerBlock * kGroupMax;  // ... this many in the pool its waves share (pool_layout.h)
 
 // per-doc header in HBM (32 B)
 struct DocHdr {
@@ -134,10 +135,12 @@ struct ReplayArgs {
   uint32_t n_keys;
   uint32_t text_base;      // arena offset of the batch's text (mte_op.a of inserts)
   unsigned long long* stats;  // n_docs * kNumStats
-  const uint32_t* pair_docs;  // pass 1: `group` document indices per wave (-1: none)
-  uint32_t n_pairs;           // pass-1 waves
-  uint32_t group;             // pass 1: documents per wave (1 .. kGroupMax)
-  unsigned long long* wclock;  // diagnostics (MTE_WAVE_CLOCK): pass-1 start / end time per pair, or null
+  // pass 1's pools (pool_layout.h), one per workgroup: first[n_pools + 1], then
+  // the flat documents; pool p holds those at [first[p], first[p + 1])
+  const uint32_t* pools;
+  uint32_t n_pools;           // pass-1 workgroups
+  uint32_t pool_max;          // documents in the largest pool (<= kPoolMax); <= kPairsPerBlock: one per wave
+  unsigned long long* wclock;  // diagnostics (MTE_WAVE_CLOCK): pass-1 start / end time per wave, or null
   unsigned long long eta;      // expected pass-1 duration in s_memrealtime ticks (0 = unknown)
   // kPack4 with a side key: the key (< 4) whose value ids may exceed a byte
   // because only marker inserts ever set it (markerId); pass 1 holds a

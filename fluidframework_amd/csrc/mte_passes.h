@@ -174,12 +174,15 @@ hipError_t launch_tree(const ReplayArgs& a, const TreeArgs& t, uint32_t blocks, 
 // the HBM tree pass (mte_htree.h): one wavefront per candidate document
 template <int K, bool S>
 hipError_t launch_htree(const ReplayArgs& a, const HtreeArgs& t, hipStream_t s);
-// pass 1 (ReplayArgs::group documents per wavefront) and pass 2 (one per
-// wavefront); pass1_waves() = the waves per SIMD pass 1's register budget is
-// built for (the host sizes the groups so the batch is resident at once)
+// pass 1 (one workgroup per pool of ReplayArgs::pools, `blocks` = n_pools) and
+// pass 2 (one document per wavefront); pass1_waves(K, S) = the waves per SIMD
+// that instantiation of pass 1 is built for, 5 or 6 (K as launch_pair takes it,
+// kPack4 included): the host lays the pools out for it (pool_layout.h), so the
+// batch is resident at once
 template <int K, bool S>
 hipError_t launch_pair(const ReplayArgs& a, uint32_t blocks, hipStream_t s);
-int pass1_waves();
+int pass1_waves(int K, bool S);
+constexpr int kPass1WavesMin = 5, kPass1WavesMax = 6;
 template <int K, bool S>
 hipError_t launch_big(const ReplayArgs& a, uint32_t blocks, hipStream_t s);
 // pass 3: HBM-streamed (mte_stream.h) or chunked (mte_chunk.h)

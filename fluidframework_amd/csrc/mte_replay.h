@@ -3,10 +3,11 @@
 // mte_regdoc.h, the steps mte_step1.h and mte_step8.h); included by the units
 // of pass 1 (mte_pass_pair.hip) and of passes 2 and 3 (mte_pass_flat.hip).
 //
-//   pair_kernel  — pass 1: `a.group` documents per wavefront (1 when the batch
-//                  fits the chip at one per wave), E <= MTE_PASS1_EMAX (<= 254
-//                  segments each at 4).  The wave runs its documents in turn,
-//                  one burst each, so all documents of a 10k-doc batch are
+//   pair_kernel  — pass 1: a workgroup per pool of documents (one document per
+//                  wave when the batch fits the chip that way), E <=
+//                  MTE_PASS1_EMAX (<= 254 segments each at 4).  The workgroup's
+//                  waves run the pool's documents one burst at a time, whichever
+//                  wave is free, so all documents of a 10k-doc batch are
 //                  resident on the chip at once (one wave per doc would need
 //                  10k resident waves; the chip holds 8 per SIMD).
 //   big_kernel   — pass 2: one document per wavefront, E in {4, 8, 16}
@@ -32,9 +33,6 @@
 #include "mte_step8.h"
 
 // Build-time knobs (tools/variants.sh builds A/B variants; defaults are the product build).
-#ifndef MTE_PAIR_WAVES  // pass-1 waves per SIMD the register budget is sized for (5: 96 VGPRs, 4: 128)
-#define MTE_PAIR_WAVES 5
-#endif
 #ifndef MTE_BURST
 #define MTE_BURST 128
 #endif
@@ -157,7 +155,7 @@ __device__ __forceinline__ void pass1_burst(DocRun& D, const ReplayArgs& a, uint
 #endif
 }
 
-// DocRun <-> a DocHdr image in LDS (pass 1 keeps both documents of a pair
+// DocRun <-> a DocHdr image in LDS (pass 1 keeps the documents of a pool
 // there between bursts, so only the running document's state occupies SGPRs)
 __device__ __forceinline__ bool run_from_lds(DocRun& D, const DocHdr* hl, int doc, const ReplayArgs& a) {
   const uint4 h0 = reinterpret_cast<const uint4*>(hl)[0], h1 = reinterpret_cast<const uint4*>(hl)[1];
@@ -199,83 +197,136 @@ __device__ __forceinline__ const ReplayArgs& args_in_place() {
   return *(const ReplayArgs*)(kargp)p;
 }
 
-// pass 1: `a.group` documents per wavefront (1 when the batch fits the chip
-// at one per wave), replayed in turn one burst each, so a 10k-document batch is
-// resident on the chip at once with the register budget of one document
-// (E <= 4); W = waves per SIMD the register budget is sized for.
+// pass 1: one workgroup per pool of documents (pool_layout.h).  A batch that
+// fits the chip at one document per wave runs that way (pool_max <= WPB: wave w
+// owns document w of its pool and nothing is shared).  A larger batch has more
+// documents in a pool than the workgroup has waves, and any wave runs any of
+// them, one burst at a time, so a 10k-document batch is resident on the chip at
+// once with the register budget of one document (E <= 4) per wave and every
+// wave slot filled; W = waves per SIMD the register budget is sized for.
+//
+// Between bursts a document lives in HBM (store_regs / load_regs) and its
+// header in the pool's LDS images `hl`, so nothing ties it to a wave.  A wave
+// claims a document with a compare-and-swap on the document's claim word in
+// LDS (lane 0, the result made uniform), runs one burst and releases it:
+//   - a document is held by at most one wave at a time;
+//   - no wave ever waits for another: the claim is one bounded scan over the
+//     pool from the wave's cursor, and a wave that finds no free document
+//     exits.  Every document with ops left is then held by a running wave,
+//     which offers it again after its burst and scans again itself (its own
+//     document last), so nothing is left behind;
+//   - the hand-off through HBM is a workgroup-scope release / acquire (the
+//     waves of a workgroup share their CU's L1): after store_regs and
+//     run_flush_stats the releasing wave fences, waits for its stores
+//     (s_waitcnt vmcnt(0) in asm: the fence's own wait can be dropped by the
+//     compiler) and only then stores the claim word; the claiming wave fences
+//     after its compare-and-swap succeeded and before load_regs.  The segment
+//     planes and the statistics are read by vector loads only (never through
+//     the scalar cache, which no fence of this scope refreshes);
+//   - the wave whose burst ends a document's part of the pass (ops done, a
+//     status, kHdrNeedsEsc, or nothing to run at all) writes its header to
+//     HBM.  A kHdrRel document is never started and its header in HBM is
+//     already what pass 1 leaves, so nobody writes it.
 //
 // Fair issue between the waves sharing a SIMD: the SIMD arbiter favours the
 // oldest wave, so with equal work per wave the youngest starves, then runs
 // alone (latency-bound) at the end: measured on config 3 the pass-1 waves
 // ended in five steps by dispatch order, 14.9 ms to 26.3 ms (tools/
-// wave_clock.py).  After every burst the wave sets its priority (4 levels)
-// from its progress against the schedule of the previous run, which keeps the
-// waves of a SIMD abreast, so they finish together.
+// wave_clock.py).  Before every burst the wave sets its priority (4 levels)
+// from the claimed document's progress against the schedule of the previous
+// run, which keeps the documents abreast, so they finish together.
+constexpr uint32_t kClaimFree = 0, kClaimHeld = 1, kClaimDone = 2;
+
 template <int K, bool S, int WPB, int W>
 __global__ __launch_bounds__(WPB * kWave, W * 4 / WPB) void pair_kernel(ReplayArgs) {
   const ReplayArgs& a = args_in_place();
   __shared__ uint32_t zlds_all[WPB][kWave * 4];
-  __shared__ DocHdr hl_all[WPB][kGroupMax];
+  __shared__ DocHdr hl[kPoolMax];
+  __shared__ uint32_t k0s[kPoolMax];    // the op cursor at the kernel's entry (for the issue priority)
+  __shared__ uint32_t claim[kPoolMax];  // kClaim*
   const int w = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-  const int pair = (int)blockIdx.x * WPB + w;
-  if (pair >= (int)a.n_pairs) return;
-  if (a.wclock && lane_id() == 0) a.wclock[2 * pair] = __builtin_amdgcn_s_memrealtime();
-  const int g = (int)a.group;
-  DocHdr* hl = hl_all[w];
-  uint32_t* zlds = zlds_all[w];
-  uint32_t live = 0;  // bit t: document t still has ops to run in this pass
-  uint32_t total = 0;  // ops of the group in this pass, and those left (for the issue priority)
-  for (int t = 0; t < g; t++) {
-    const int doc = (int)a.pair_docs[(uint32_t)g * (uint32_t)pair + (uint32_t)t];
-    if (doc >= 0) {
-      DocHdr h = a.hdr[doc];
-      const bool rel = (h.flags & kHdrRel) != 0;  // the streamed pass's this batch
-      if (!rel) h.flags &= ~kHdrNeedsEsc;
-      if (lane_id() == 0) hl[t] = h;
-      if (!rel) {
-        live |= 1u << t;
-        total += (uint32_t)(a.op_off[doc + 1] - a.op_off[doc]) - h.resume;
-      }
-    }
+  const uint32_t wave = blockIdx.x * WPB + (uint32_t)w;
+  if (a.wclock && lane_id() == 0) a.wclock[2 * wave] = __builtin_amdgcn_s_memrealtime();
+  // (made uniform by hand: the table is read by vector loads, and the pointer
+  // would otherwise sit in a VGPR pair across the op loop)
+  const uint32_t first = uni(a.pools[blockIdx.x]);
+  const uint32_t n = min(uni(a.pools[blockIdx.x + 1]) - first, (uint32_t)kPoolMax);
+  uint64_t docs_at = reinterpret_cast<uint64_t>(a.pools + a.n_pools + 1 + first);
+  asm("" : "+s"(docs_at));
+  const uint32_t* const docs = reinterpret_cast<const uint32_t*>(docs_at);
+  // the pool's headers into LDS, one thread per document
+  if (threadIdx.x < n) {
+    const uint32_t t = threadIdx.x;
+    DocHdr h = a.hdr[docs[t]];
+    const bool rel = (h.flags & kHdrRel) != 0;  // the streamed pass's this batch
+    if (!rel) h.flags &= ~kHdrNeedsEsc;
+    hl[t] = h;
+    k0s[t] = h.resume;
+    claim[t] = rel ? kClaimDone : kClaimFree;
   }
-  fence_wave();
-  total = uni(total);
-  uint32_t left = total;
+  __syncthreads();
+  uint32_t* zlds = zlds_all[w];
+  const bool owned = a.pool_max <= (uint32_t)WPB;  // one document per wave
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
   __builtin_amdgcn_s_setprio(2);
-  // one burst per iteration, the documents in turn; a single copy of the
-  // burst code serves them all (the document is a runtime index)
-  for (int t = 0; live; t = (t + 1 == g) ? 0 : t + 1) {
-    if (!(live & (1u << t))) continue;
-    const int doc = (int)a.pair_docs[(uint32_t)g * (uint32_t)pair + (uint32_t)t];
+  // one burst per iteration; a single copy of the burst code serves every
+  // document (the document is a runtime index)
+  uint32_t t = (uint32_t)w < n ? (uint32_t)w : 0u;  // the cursor
+  bool more = owned ? (uint32_t)w < n && claim[w] == kClaimFree : n != 0;
+  while (more) {
+    if (!owned) {
+      uint32_t got = n;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t c = t + i < n ? t + i : t + i - n;
+        uint32_t seen = kClaimHeld;
+        if (lane_id() == 0) {
+          seen = kClaimFree;
+          __hip_atomic_compare_exchange_strong(&claim[c], &seen, kClaimHeld, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (uni(seen) == kClaimFree) {
+          got = c;
+          break;
+        }
+      }
+      if (got == n) break;  // every document is done or held by a running wave
+      t = got;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    const int doc = uni((int32_t)docs[t]);
     DocRun D;
-    const uint32_t k0 = hl[t].resume;
-    if (run_from_lds(D, &hl[t], doc, a)) pass1_burst<K, S>(D, a, zlds);
+    if (run_from_lds(D, &hl[t], doc, a)) {
+      // against the schedule of the previous run (a.eta ticks for the whole
+      // pass; a first run's is estimated from the batch, mte_run): the
+      // document behind it -> higher priority for its burst
+      if (a.eta) {
+        const uint32_t k0 = uni(k0s[t]);
+        const unsigned long long total = D.k1 - k0;
+        const unsigned long long el = __builtin_amdgcn_s_memrealtime() - t_start;
+        const unsigned long long mine = (unsigned long long)(D.k - k0) * a.eta;  // done/total vs el/eta
+        const unsigned long long sched = el * total;
+        const unsigned long long band = total * a.eta / 32;
+        if (mine + band < sched) __builtin_amdgcn_s_setprio(3);
+        else if (mine < sched) __builtin_amdgcn_s_setprio(2);
+        else if (mine < sched + band) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+      }
+      pass1_burst<K, S>(D, a, zlds);
+    }
     run_to_lds(D, &hl[t]);
-    if (!D.running) live &= ~(1u << t);
-    const uint32_t ran = uni(hl[t].resume - k0);
-    left -= ran;
-    // against the schedule of the previous run (a.eta ticks for the whole
-    // pass; a first run's is estimated from the batch, mte_run): behind it ->
-    // higher priority
-    if (a.eta) {
-      const unsigned long long el = __builtin_amdgcn_s_memrealtime() - t_start;
-      const unsigned long long mine = (unsigned long long)(total - left) * a.eta;  // done/total vs el/eta
-      const unsigned long long sched = el * total;
-      const unsigned long long band = (unsigned long long)total * a.eta / 32;
-      if (mine + band < sched) __builtin_amdgcn_s_setprio(3);
-      else if (mine < sched) __builtin_amdgcn_s_setprio(2);
-      else if (mine < sched + band) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
+    if (!D.running && lane_id() == 0) a.hdr[doc] = hl[t];  // resume = the op cursor
+    if (owned) {
+      more = D.running;
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane_id() == 0)
+        __hip_atomic_store(&claim[t], D.running ? kClaimFree : kClaimDone, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+      t = t + 1 == n ? 0 : t + 1;
     }
   }
-  if (lane_id() == 0) {
-    for (int t = 0; t < g; t++) {
-      const int doc = (int)a.pair_docs[(uint32_t)g * (uint32_t)pair + (uint32_t)t];
-      if (doc >= 0) a.hdr[doc] = hl[t];  // resume = the op cursor
-    }
-    if (a.wclock) a.wclock[2 * pair + 1] = __builtin_amdgcn_s_memrealtime();
-  }
+  if (a.wclock && lane_id() == 0) a.wclock[2 * wave + 1] = __builtin_amdgcn_s_memrealtime();
 }
 
 // pass 2: one document per wavefront, for the documents pass 1 escalated

@@ -3,8 +3,9 @@
 # product library is fluidframework_amd/_lib/libmte.so).  The flat-pass
 # and chunk-pass translation units are rebuilt with the variant's flags and
 # linked with the product's other objects (make -C fluidframework_amd/csrc first).
-# The knobs are the build-time macros of mte_replay.h (MTE_PAIR_WAVES, MTE_BURST,
-# MTE_PASS1_EMAX) and the diagnostic switches of the other passes.  The rejected
+# The knobs are the build-time macros of mte_replay.h (MTE_BURST, MTE_PASS1_EMAX)
+# and the diagnostic switches of the other passes.  Pass 1's waves per SIMD are
+# set per instantiation (pair_waves, mte_pass_pair.hip), not by a macro.  The rejected
 # kernels DESIGN.md §6 measures (mte_lean.h, mte_rsmall.h) are not in the tree:
 # tools/variants/ held them last at commit 58eea73.
 # Usage: variants.sh name:"flags" ...   e.g. variants.sh w5e2:"-DMTE_PASS1_EMAX=2"
