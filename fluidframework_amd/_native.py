@@ -60,6 +60,7 @@ def load_mte():
         "mte_read_texts": ([vp, vp, u32, vp, vp, C.c_uint64, vp], C.c_int),
         "mte_props_at": ([vp, vp, u32, vp, vp], C.c_int),
         "mte_read_ref_positions": ([vp, vp, u32, vp, vp, vp, C.c_uint64], C.c_int),
+        "mte_read_segment_lists": ([vp, vp, u32, vp, vp, vp, u64, vp, u64, vp, vp], C.c_int),
         "mte_doc_status": ([vp, vp, u32], C.c_int),
         "mte_stats_get": ([vp, vp], C.c_int),
         "mte_set_stats": ([vp, C.c_int], C.c_int),

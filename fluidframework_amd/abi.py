@@ -125,6 +125,24 @@ assert REF_QUERY_DTYPE.itemsize == 16
 REF_INFO_DTYPE = np.dtype([("status", "<i4"), ("cur_seq", "<i4"), ("min_seq", "<i4"), ("length", "<u4"),
                            ("offset", "<u8")])
 assert REF_INFO_DTYPE.itemsize == 24
+# mte_read_segment_lists: a query and its answer's header
+SEGS_RAW, SEGS_V1, SEGS_LEGACY = 0, 1, 2
+SEGS_DOC_MIN_SEQ = 0x1
+SEGS_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("mode", "<u4"), ("min_seq", "<i4"), ("flags", "<u4")])
+assert SEGS_QUERY_DTYPE.itemsize == 16
+SEGS_INFO_DTYPE = np.dtype([("status", "<i4"), ("cur_seq", "<i4"), ("min_seq", "<i4"), ("n_segs", "<u4"),
+                            ("n_text", "<u4"), ("reserved", "<u4"), ("seg_offset", "<u8"), ("text_offset", "<u8")])
+assert SEGS_INFO_DTYPE.itemsize == 40
+
+
+class MteSegsQuery(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("mode", C.c_uint32), ("min_seq", C.c_int32), ("flags", C.c_uint32)]
+
+
+class MteSegsInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("cur_seq", C.c_int32), ("min_seq", C.c_int32), ("n_segs", C.c_uint32),
+                ("n_text", C.c_uint32), ("reserved", C.c_uint32), ("seg_offset", C.c_uint64),
+                ("text_offset", C.c_uint64)]
 
 
 class MteRefQuery(C.Structure):
@@ -197,7 +215,7 @@ EXPORTED_SYMBOLS = [
     "mte_comm_unique_id", "mte_comm_init", "mte_comm_share", "mte_comm_barrier", "mte_comm_allreduce_f64",
     "mte_comm_gather_digests", "mte_comm_world", "mte_comm_destroy", "mte_read_deltas", "mte_set_event_capacity",
     "mte_set_ref_capacity", "mte_read_refs", "mte_read_refs_transient", "mte_read_ref_order", "mte_find_tiles",
-    "mte_read_texts", "mte_props_at", "mte_read_ref_positions",
+    "mte_read_texts", "mte_props_at", "mte_read_ref_positions", "mte_read_segment_lists",
 ]
 
 DOC_EVENTS = 0x8

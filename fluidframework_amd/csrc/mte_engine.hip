@@ -730,6 +730,9 @@ struct mte_ctx {
   // mte_read_ref_positions: the queries (2 words each) then the tasks (2 words each);
   // the infos (3 words each), the order keys, the positions (two a word)
   DevBuf<uint64_t> ref_in, ref_out;
+  // mte_read_segment_lists: the queries (2 words each) then the infos (5 words each);
+  // the rows (4 words each), the property rows, the units
+  DevBuf<uint64_t> segs_in, segs_out;
   // per key, the largest property value id the context was given (load +
   // every batch) and whether any text segment or annotate ever carried it:
   // pass 1 packs the 4 property planes into one (kPack4) when every key's ids
@@ -1364,6 +1367,7 @@ int mte_destroy(mte_ctx* c) {
   free_buf(c->tile_in), free_buf(c->tile_out);
   free_buf(c->text_in), free_buf(c->text_info), free_buf(c->text_out);
   free_buf(c->ref_in), free_buf(c->ref_out);
+  free_buf(c->segs_in), free_buf(c->segs_out);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->tree_stream) (void)hipStreamDestroy(c->tree_stream);
@@ -2399,6 +2403,77 @@ int mte_read_ref_positions(mte_ctx* c, const mte_ref_query* q, uint32_t n, mte_r
   std::memcpy(info, res.data(), iw * 8);
   if (order && total) std::memcpy(order, res.data() + iw, total * 8);
   if (pos && total) std::memcpy(pos, res.data() + iw + ow, total * 4);
+  return MTE_OK;
+}
+
+int mte_read_segment_lists(mte_ctx* c, const mte_segs_query* q, uint32_t n, mte_segs_info* info, mte_seg* segs,
+                           uint32_t* props, uint64_t seg_cap, uint16_t* text, uint64_t text_cap, uint64_t* n_segs_total,
+                           uint64_t* n_text_total) {
+  if (!c || !n_segs_total || !n_text_total || (n && (!q || !info))) return MTE_E_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++) {
+    const mte_segs_query& t = q[i];
+    if (t.doc >= c->docs.n_docs || t.mode > MTE_SEGS_LEGACY || (t.flags & ~MTE_SEGS_DOC_MIN_SEQ) ||
+        (t.min_seq < 0 && !(t.flags & MTE_SEGS_DOC_MIN_SEQ)))
+      return set_err(c, MTE_E_INVALID_ARG, "mte_read_segment_lists: query %u (doc %u, mode %u, min_seq %d, flags 0x%x)", i,
+                     t.doc, t.mode, t.min_seq, t.flags);
+  }
+  JOIN_TAIL(c);
+  *n_segs_total = *n_text_total = 0;
+  if (!n) return MTE_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  static_assert(sizeof(mte_segs_query) == 16 && sizeof(mte_segs_info) == 40 && sizeof(mte_seg) == 32,
+                "mte_read_segment_lists packs these as 64-bit words");
+  // the queries up, the count, the infos down (the first wait) ...
+  const uint64_t qw = 2ull * n, iw = 5ull * n;
+  if (int rc = grow(c, c->segs_in, qw + iw)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->segs_in.p, q, 16ull * n, hipMemcpyHostToDevice, c->stream));
+  SegsArgs a;
+  a.hdr = c->docs.hdr;
+  a.soa = c->docs.soa;
+  a.cap = c->cap;
+  a.n_keys = c->n_keys;
+  a.n = n;
+  a.lazy = c->docs.rounds_carried ? 1u : 0u;
+  a.tree = c->docs.d_tree;  // null without tree documents: read only for a doc_has_tree document
+  // the plane is there when some document has a local client or MTE_DOC_TREE, and read only for those
+  a.rm_hi = nullptr;
+  for (uint32_t f : c->docs.flags)
+    if (f & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) {
+      a.rm_hi = reinterpret_cast<const uint32_t*>(c->docs.soa.len) + (uint64_t)rm_hi_plane((int)c->kt) * c->docs.soa.plane_stride;
+      break;
+    }
+  a.q = (const mte_segs_query*)c->segs_in.p;
+  a.info = (mte_segs_info*)(c->segs_in.p + qw);
+  a.arena = c->arena.p;
+  a.segs = nullptr;
+  a.props = nullptr;
+  a.text = nullptr;
+  HIPCHK(c, launch_segs_count(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, a.info, 40ull * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint64_t ts = 0, tt = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    info[i].seg_offset = ts;
+    info[i].text_offset = tt;
+    ts += info[i].n_segs;
+    tt += info[i].n_text;
+  }
+  *n_segs_total = ts;
+  *n_text_total = tt;
+  if (ts > seg_cap || tt > text_cap || (ts && (!segs || (c->n_keys && !props))) || (tt && !text) || !ts) return MTE_OK;
+  // ... the offsets up, the gather, the rows, property rows and units down (the second)
+  const uint64_t sw = 4ull * ts, pw = ((uint64_t)ts * c->n_keys + 1) / 2, xw = (tt + 3) / 4;
+  if (int rc = grow(c, c->segs_out, sw + pw + xw)) return rc;
+  a.info = (mte_segs_info*)(c->segs_in.p + qw);  // (grow leaves segs_in alone)
+  HIPCHK(c, hipMemcpyAsync(a.info, info, 40ull * n, hipMemcpyHostToDevice, c->stream));
+  a.segs = (mte_seg*)c->segs_out.p;
+  a.props = (uint32_t*)(c->segs_out.p + sw);
+  a.text = (uint16_t*)(c->segs_out.p + sw + pw);
+  HIPCHK(c, launch_segs_gather(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(segs, a.segs, 32ull * ts, hipMemcpyDeviceToHost, c->stream));
+  if (c->n_keys) HIPCHK(c, hipMemcpyAsync(props, a.props, 4ull * ts * c->n_keys, hipMemcpyDeviceToHost, c->stream));
+  if (tt) HIPCHK(c, hipMemcpyAsync(text, a.text, 2ull * tt, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MTE_OK;
 }
 

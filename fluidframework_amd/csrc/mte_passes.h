@@ -257,4 +257,26 @@ struct RefArgs {
 };
 hipError_t launch_ref_positions(const RefArgs& a, hipStream_t s);
 
+// mte_read_segment_lists: segs_count_kernel fills info (all but the offsets),
+// the host sums the counts into offsets and sends info back, segs_gather_kernel
+// repeats the walk and writes rows, property rows and units
+struct SegsArgs {
+  const DocHdr* hdr;
+  SegSoA soa;
+  uint32_t cap;
+  uint32_t n_keys;
+  uint32_t n;                  // queries; one wave each
+  uint32_t lazy;               // docs.rounds_carried: a flat document may hold tombstones at or below its minSeq
+  const uint32_t* tree;        // the tree words; null in a context without tree documents
+  const uint32_t* rm_hi;       // the removers of short ids 32 .. 63 (rm_hi_plane); null without such documents
+  const mte_segs_query* q;     // validated by the host (doc, mode, min_seq, flags)
+  mte_segs_info* info;         // [n]: written by the count, read (status, offsets) by the gather
+  const uint16_t* arena;
+  mte_seg* segs;               // (gather)
+  uint32_t* props;             // (gather) [row][n_keys]
+  uint16_t* text;              // (gather)
+};
+hipError_t launch_segs_count(const SegsArgs& a, hipStream_t s);
+hipError_t launch_segs_gather(const SegsArgs& a, hipStream_t s);
+
 }  // namespace mte

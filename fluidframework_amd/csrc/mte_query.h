@@ -71,6 +71,33 @@
 // as the gfx950 -O3 build reports.  One wave walks a whole document per
 // 64 slots: correct, slow for a document of a million segments; no
 // tile-parallel variant is built.
+//
+// segs_count_kernel and segs_gather_kernel answer mte_read_segment_lists: the
+// list mte_read_segments returns (MTE_SEGS_RAW) for any number of documents, or
+// that list dropped and coalesced as SnapshotV1.extractSegment
+// (snapshotV1.ts:189-265, MTE_SEGS_V1) and SnapshotLegacy.extractSync
+// (snapshotlegacy.ts:153-211, MTE_SEGS_LEGACY) reduce it at a minSeq.  One wave
+// per query, four per workgroup; both kernels run segs_walk, 64 slots a step:
+// rseq, seq, len, meta, toff coalesced, the tree word only where doc_has_tree,
+// the property planes and one arena unit a lane (the slot's last) only in the
+// coalescing modes.  A kTCont slot takes the class of its head, a kept slot
+// pulls the class, last unit and property row of the kept slot before it
+// (ballot, lane-mask count, ds_bpermute), and the one sequential condition of
+// TextSegment.canAppend is taken in closed form over a scan of the kept
+// lengths: inside a chain joined by every other condition, slot i starts a new
+// row exactly when len(i) > 256 and the kept units since the chain's head
+// exceed 256.  What crosses a step is wave-uniform: the last kept slot's class,
+// last unit and property row, the units since the chain's head, the counts, the
+// open row's length.  The count writes the counts; the host turns them into
+// offsets; the gather repeats the walk, each row's start lane writes its fields
+// and property row, a row's len is written when its run closes (in the step, at
+// a later step's first start, or at the document's end), and the text is copied
+// unit-parallel as text_gather_kernel does it (per-wave LDS staging, the 6-step
+// search).  Reads of engine state only; plain vector stores of the answers.
+// 256 threads; count: 37 VGPRs, no LDS, no scratch; gather: 53 VGPRs, 2 KiB of
+// LDS a workgroup, no scratch, as the gfx950 -O3 build reports.  One wave walks
+// a whole document: correct, slow for a document of a million segments; no
+// tile-parallel variant is built.
 #pragma once
 
 #include "mte_kernels.h"
@@ -386,6 +413,253 @@ __global__ __launch_bounds__(256) void ref_positions_kernel(RefArgs a) {
     o->length = (uint32_t)carry;
     o->offset = out0;
   }
+}
+
+// ---- mte_read_segment_lists ---------------------------------------------------
+constexpr int32_t kSegGranularity = 256;  // TextSegmentGranularity (textSegment.ts)
+
+__device__ __forceinline__ int top_lane(unsigned long long b) { return 63 - __builtin_clzll(b); }
+__device__ __forceinline__ uint32_t pull(int lane, uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_ds_bpermute(lane << 2, (int32_t)v);
+}
+
+// The walk both kernels run, so they agree slot for slot.  Per 64-slot step a
+// slot is valid (it gives something to the raw list), a head (it opens a raw
+// segment) or a follower (a kTCont slot behind a head), kept (the mode keeps its
+// raw segment) and, a kept head, the start of an output row or joined to the row
+// before it.  The class word w of a lane: bit 0 kept, bit 1 eligible, bits 2..
+// the kind; a follower takes its head's.
+template <bool GATHER>
+__device__ __forceinline__ void segs_walk(const SegsArgs& a, uint32_t qi, int l, uint2* st) {
+  const mte_segs_query q = a.q[qi];
+  const uint32_t doc = uni(q.doc), mode = uni(q.mode);
+  const DocHdr h = a.hdr[doc];
+  const int32_t dmin = uni(h.min_seq);
+  const int32_t m = (uni(q.flags) & MTE_SEGS_DOC_MIN_SEQ) ? dmin : uni(q.min_seq);
+  const uint32_t hflags = uni(h.flags);
+  int n = h.status == MTE_OK ? h.nseg : 0;
+  n = uni(n < 0 ? 0 : (n > (int)a.cap ? (int)a.cap : n));
+  uint64_t so = 0, to = 0;
+  if constexpr (GATHER) {
+    const mte_segs_info* o = a.info + qi;
+    if (uni(o->status) != MTE_OK || uni(o->n_segs) == 0u) return;  // the count refused it, or nothing to write
+    so = uni64(o->seg_offset);
+    to = uni64(o->text_offset);
+  }
+  const uint64_t db = (uint64_t)doc * a.cap;
+  const bool tree = doc_has_tree(hflags);
+  const bool rmhi = (hflags & (MTE_DOC_LOCAL_CLIENT | MTE_DOC_TREE)) != 0 && a.rm_hi != nullptr;
+  const bool lazy = a.lazy != 0 && !tree;
+  const bool coal = mode != MTE_SEGS_RAW, legacy = mode == MTE_SEGS_LEGACY;
+  const int nk = (int)a.n_keys;
+  const unsigned long long me = 1ull << l, lt = me - 1;
+
+  // carried from step to step, wave-uniform
+  bool any = false;     // a raw segment was opened
+  bool keep_a = false;  // the open raw segment is kept
+  uint32_t bw = 0, blast = 0, bp[MTE_MAX_KEYS] = {};  // the last kept slot: class word, last unit, property row
+  int32_t run = 0;       // kept units since the head of the soft run
+  uint32_t nrows = 0, ntext = 0;
+  int32_t open_len = 0;  // units of row nrows - 1 so far
+  bool bad = false;
+
+  for (int c0 = 0; c0 < n; c0 += kWave) {
+    const int i = c0 + l;
+    const bool in = i < n;
+    const uint32_t tw = (in && tree) ? a.tree[db + i] : 0u;
+    const int32_t rs = in ? a.soa.rseq[db + i] : kNone;
+    const int32_t sq = in ? a.soa.seq[db + i] : 0;
+    const int32_t L = in ? a.soa.len[db + i] : 0;
+    const uint32_t meta = in ? a.soa.meta[db + i] : 0u;
+    const uint32_t toff = in ? a.soa.toff[db + i] : 0u;
+    if constexpr (!GATHER)
+      if (rmhi) bad |= in && a.rm_hi[db + i] != 0u && !(tw & kTEmpty) && rs != kNone;
+    const bool valid = in && !(tw & kTEmpty) && !(lazy && rs != kNone && rs <= dmin);
+    const unsigned long long bv = __ballot(valid);
+    const bool head = valid && (!(tw & kTCont) || (!any && (bv & lt) == 0));
+    const unsigned long long bh = __ballot(head);
+    const uint32_t kind = meta >> 8;
+    bool keep = true, elig = false;
+    if (coal) {
+      keep = legacy ? (sq <= m && rs > m) : !(rs != kNone && rs <= m);
+      elig = legacy ? keep : (rs == kNone && sq <= m);
+    }
+    uint32_t w = (keep ? 1u : 0u) | (elig ? 2u : 0u) | (kind << 2);
+    uint32_t p[MTE_MAX_KEYS];
+#pragma unroll
+    for (int k = 0; k < MTE_MAX_KEYS; k++)
+      p[k] = (k < nk && head && (coal || GATHER)) ? a.soa.props[(uint64_t)k * a.soa.plane_stride + db + i] : 0u;
+
+    // a raw segment's units past this step (its kTCont slots there): the length rule asks for all of them
+    int32_t ext = 0;
+    if (coal && tree && bh) {
+      for (int c1 = c0 + kWave; c1 < n; c1 += kWave) {
+        const int j = c1 + l;
+        const uint32_t t2 = j < n ? a.tree[db + j] : kTEmpty;
+        const int32_t l2 = j < n ? a.soa.len[db + j] : 0;
+        const bool v2 = !(t2 & kTEmpty);
+        const unsigned long long stop = __ballot(v2 && !(t2 & kTCont));
+        const unsigned long long before = stop ? ((stop & (~stop + 1ull)) - 1ull) : ~0ull;
+        ext += rdlane(wave_incl_scan((v2 && (before & me)) ? l2 : 0), kWave - 1);
+        if (stop) break;
+      }
+    }
+
+    // a follower takes its head's class (and, where rows are compared, its property row)
+    const bool follower = valid && !head;
+    {
+      const unsigned long long hb = bh & lt;
+      const int hl = hb ? top_lane(hb) : 0;
+      const uint32_t wh = pull(hl, w);
+      if (follower) w = hb ? wh : (keep_a ? bw : 0u);
+      if (coal) {
+#pragma unroll
+        for (int k = 0; k < MTE_MAX_KEYS; k++)
+          if (k < nk) {
+            const uint32_t ph = pull(hl, p[k]);
+            if (follower) p[k] = hb ? ph : bp[k];
+          }
+      }
+    }
+    const bool kept = valid && (w & 1u);
+    const bool e = (w & 2u) != 0;
+    const uint32_t ekind = w >> 2;
+    const unsigned long long bk = __ballot(kept);
+    const bool gives = kept && (head ? kind == 0 : true);  // units for `text`
+    uint32_t last = 0;
+    if (coal && kept && ekind == 0 && L > 0) last = a.arena[toff + (uint32_t)(L - 1)];
+
+    // the kept slot before this one: soft = joined to it by every condition but the length one
+    bool soft = false;
+    if (coal) {
+      const unsigned long long kb = bk & lt;
+      const int pl = kb ? top_lane(kb) : 0;
+      uint32_t pw = pull(pl, w), plast = pull(pl, last);
+      if (!kb) pw = bw, plast = blast;
+      bool same = true, uneq = false;
+#pragma unroll
+      for (int k = 0; k < MTE_MAX_KEYS; k++)
+        if (k < nk) {
+          const uint32_t pk = pull(pl, p[k]);
+          same = same && (kb ? pk : bp[k]) == p[k];
+          uneq = uneq || (p[k] & MTE_VALUE_UNEQUAL);
+        }
+      soft = kept && head && e && (pw & 3u) == 3u && ekind == 0 && (pw >> 2) == 0 && plast != 0x0Au && same && !uneq;
+    }
+    const int32_t KL = kept ? L : 0;
+    const int32_t kin = wave_incl_scan(KL);
+    const int32_t S = kin - KL;
+    const int32_t total = rdlane(kin, kWave - 1);
+    const bool rh = kept && head && !soft;  // the head of a soft run
+    const unsigned long long brh = __ballot(rh);
+    bool brk = false;
+    if (coal) {
+      // the raw segment's length: to the next head, or past the step's end
+      int32_t rawlen = L;
+      if (tree) {
+        const int32_t VL = valid ? L : 0;
+        const int32_t vin = wave_incl_scan(VL);
+        const unsigned long long ha = bh & ~(lt | me);
+        const int32_t vnh = (int32_t)pull(ha ? __builtin_ctzll(ha) : 0, (uint32_t)(vin - VL));
+        rawlen = (ha ? vnh : rdlane(vin, kWave - 1) + ext) - (vin - VL);
+      }
+      const unsigned long long rb = brh & (lt | me);
+      const int32_t Sh = (int32_t)pull(rb ? top_lane(rb) : 0, (uint32_t)S);
+      const int32_t d = rb ? S - Sh : run + S;  // S(i) - S(h)
+      brk = soft && rawlen > kSegGranularity && d > kSegGranularity;
+    }
+    const bool start = kept && head && (!soft || brk);
+    const unsigned long long bs = __ballot(start);
+    const int32_t TL = gives ? L : 0;
+    const int32_t tin = wave_incl_scan(TL);
+    const int32_t T = rdlane(tin, kWave - 1);
+
+    if constexpr (GATHER) {
+      const uint32_t rmask = (start && rs != kNone) ? a.soa.rmask[db + i] : 0u;
+      const unsigned long long sa = bs & ~(lt | me);
+      const int32_t Snx = (int32_t)pull(sa ? __builtin_ctzll(sa) : 0, (uint32_t)S);
+      if (start) {
+        const uint64_t r = so + nrows + (uint32_t)__builtin_popcountll(bs & lt);
+        mte_seg* row = a.segs + r;
+        const bool info_kept = !coal || (!e && sq > m);  // seq and client stay
+        row->text_off = kind == 0 ? ntext + (uint32_t)(tin - TL) : 0u;
+        if (sa) row->len = (uint32_t)(Snx - S);
+        row->seq = info_kept ? sq : 0;
+        row->removed_seq = e ? MTE_NOT_REMOVED : rs;  // kNone is MTE_NOT_REMOVED
+        row->removers = e ? 0u : rmask;
+        row->client = info_kept ? (int32_t)(meta & 0xffu) - 1 : -1;
+        row->kind = kind;
+        row->propset = MTE_NO_PROPS;
+#pragma unroll
+        for (int k = 0; k < MTE_MAX_KEYS; k++)
+          if (k < nk) a.props[r * (uint64_t)nk + k] = p[k];
+      }
+      // the row open since an earlier step closes at this step's first start
+      if (bs && nrows > 0 && (bs & lt) == 0 && start) a.segs[so + nrows - 1].len = (uint32_t)(open_len + S);
+      if (T > 0) {
+        uint16_t* out = a.text + to + ntext;
+        st[l] = make_uint2((uint32_t)(tin - TL), toff);
+        query_fence_wave();
+        for (int32_t j = l; j < T; j += kWave) {
+          int s = 0;  // the last slot whose exclusive sum is <= j: the giving one (text_gather_kernel)
+#pragma unroll
+          for (int b = kWave / 2; b > 0; b >>= 1)
+            if ((int32_t)st[s + b].x <= j) s += b;
+          const uint2 x = st[s];
+          out[j] = a.arena[x.y + (uint32_t)(j - (int32_t)x.x)];
+        }
+        query_fence_wave();  // the next step overwrites the slice
+      }
+    }
+
+    if (bs) open_len = total - rdlane(S, top_lane(bs));
+    else open_len += total;
+    nrows += (uint32_t)__builtin_popcountll(bs);
+    ntext += (uint32_t)T;
+    if (brh) run = total - rdlane(S, top_lane(brh));
+    else run += total;
+    if (bk) {
+      const int lk = top_lane(bk);
+      bw = rdlane(w, lk);
+      blast = rdlane(last, lk);
+      if (coal) {
+#pragma unroll
+        for (int k = 0; k < MTE_MAX_KEYS; k++)
+          if (k < nk) bp[k] = rdlane(p[k], lk);
+      }
+    }
+    if (bv) {
+      keep_a = (rdlane(w, top_lane(bv)) & 1u) != 0;
+      any = true;
+    }
+  }
+  if constexpr (GATHER) {
+    if (nrows > 0 && l == 0) a.segs[so + nrows - 1].len = (uint32_t)open_len;
+  } else {
+    const bool refused = __ballot(bad) != 0;  // mte_read_segments refuses the document
+    if (l == 0) {
+      mte_segs_info* o = a.info + qi;  // the offsets are the host's
+      o->status = refused ? MTE_E_UNSUPPORTED : h.status;
+      o->cur_seq = h.cur_seq;
+      o->min_seq = h.min_seq;
+      o->n_segs = refused ? 0u : nrows;
+      o->n_text = refused ? 0u : ntext;
+      o->reserved = 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void segs_count_kernel(SegsArgs a) {
+  const uint32_t qi = blockIdx.x * kQueriesPerBlock + threadIdx.x / kWave;
+  if (qi >= a.n) return;
+  segs_walk<false>(a, qi, lane_id(), nullptr);
+}
+
+__global__ __launch_bounds__(256) void segs_gather_kernel(SegsArgs a) {
+  __shared__ uint2 stage[kQueriesPerBlock][kWave];  // (exclusive sum, arena offset)
+  const uint32_t qi = blockIdx.x * kQueriesPerBlock + threadIdx.x / kWave;
+  if (qi >= a.n) return;
+  segs_walk<true>(a, qi, lane_id(), stage[threadIdx.x / kWave]);
 }
 
 }  // namespace mte

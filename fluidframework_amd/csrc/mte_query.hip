@@ -32,4 +32,14 @@ hipError_t launch_ref_positions(const RefArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_segs_count(const SegsArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(segs_count_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_segs_gather(const SegsArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(segs_gather_kernel, dim3(query_blocks(a.n)), dim3(kQueriesPerBlock * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace mte

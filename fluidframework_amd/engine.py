@@ -12,6 +12,7 @@ import numpy as np
 from . import _native
 from .abi import (DELTA_DTYPE, DOC_INIT_DTYPE, EXPORTED_SYMBOLS, OP_DTYPE, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE,
                   POS_HIT_DTYPE, POS_QUERY_DTYPE, REF_INFO_DTYPE, REF_QUERY_DTYPE, REFS_TRANSIENT,
+                  SEGS_DOC_MIN_SEQ, SEGS_INFO_DTYPE, SEGS_QUERY_DTYPE,
                   TEXT_INFO_DTYPE, TEXT_PLACEHOLDERS, TEXT_QUERY_DTYPE, TEXT_TO_END,
                   TILE_HIT_DTYPE, TILE_PRECEDING, TILE_QUERY_DTYPE,
                   MergeTreeError, MteBatch, MteConfig, MteDocView, MteSegList, MteStats, ptr)
@@ -128,6 +129,27 @@ class EngineBase:
         self._check(self._read_segments(doc, C.byref(v)), "read_segments")
         n = v.n_segs
         return segs[:n], props[: n * self.n_keys].reshape(n, self.n_keys), text[: v.n_text]
+
+    def read_segment_lists(self, queries, info=False):
+        """Segment lists for many documents at once: queries = [(doc, mode,
+        min_seq)], mode abi.SEGS_RAW (read_segments' list), SEGS_V1 or
+        SEGS_LEGACY (that list reduced as a summary writer reduces it at
+        min_seq; None: the document's own minSeq) -> [(segs, props, text)], and
+        with info=True also [{status, cur_seq, min_seq}] per query.  Here
+        through the per-document read_segments and snapshot.reduce_segments;
+        DeviceEngine answers all of them by one device call (include/mte.h
+        mte_read_segment_lists).  Raises MergeTreeError for a document whose
+        status is not OK."""
+        from .snapshot import reduce_segments
+        lists, infos = [], []
+        for doc, mode, min_seq in queries:
+            v = self.read_doc(doc)
+            if v["status"] != 0:
+                raise MergeTreeError(int(v["status"]), f"read_segment_lists: document {int(doc)}")
+            infos.append({k: v[k] for k in ("status", "cur_seq", "min_seq")})
+            segs, props, text = self.read_segments(doc)
+            lists.append(reduce_segments(segs, props, text, mode, v["min_seq"] if min_seq is None else min_seq))
+        return (lists, infos) if info else lists
 
     def digest(self):
         out = np.zeros(self.n_docs * 4, np.uint64)
@@ -390,6 +412,56 @@ class DeviceEngine(EngineBase):
         if not order:
             return out
         return out, ([a.copy() for a in np.split(keys, cuts)] if len(q) else [])
+
+    def read_segment_lists_raw(self, q):
+        """mte_read_segment_lists over SEGS_QUERY_DTYPE[n] -> (SEGS_INFO_DTYPE[n],
+        SEG_DTYPE[rows], uint32[rows, n_keys], uint16 units): query i's rows at
+        info["seg_offset"][i] .. + info["n_segs"][i], its units at
+        info["text_offset"][i] .. + info["n_text"][i], from one device call (two
+        when the host buffers have to grow first)."""
+        q = _arr(q, SEGS_QUERY_DTYPE)
+        info = np.zeros(len(q), SEGS_INFO_DTYPE)
+        ns, nt = C.c_uint64(), C.c_uint64()
+        nk = max(self.n_keys, 1)
+        bufs = getattr(self, "_segs_bufs", None)
+        if bufs is None:
+            bufs = self._segs_bufs = (np.zeros(1 << 12, SEG_DTYPE), np.zeros((1 << 12) * nk, np.uint32),
+                                      np.zeros(1 << 16, np.uint16))
+
+        def call():
+            segs, props, text = self._segs_bufs
+            self._check(self.lib.mte_read_segment_lists(self.ctx, ptr(q), len(q), ptr(info), ptr(segs), ptr(props),
+                                                        len(segs), ptr(text), len(text), C.byref(ns), C.byref(nt)),
+                        "read_segment_lists")
+        call()
+        if ns.value > len(bufs[0]) or nt.value > len(bufs[2]):  # size-then-fill: nothing was written
+            rows = max(2 * ns.value, len(bufs[0]))
+            self._segs_bufs = (np.zeros(rows, SEG_DTYPE), np.zeros(rows * nk, np.uint32),
+                               np.zeros(max(2 * nt.value, len(bufs[2])), np.uint16))
+            call()
+        segs, props, text = self._segs_bufs
+        n = ns.value
+        return (info, segs[:n].copy(), props[: n * self.n_keys].reshape(n, self.n_keys).copy(),
+                text[: nt.value].copy())
+
+    def read_segment_lists(self, queries, info=False):
+        """EngineBase.read_segment_lists by one device call for all queries
+        (include/mte.h mte_read_segment_lists).  One wavefront walks a queried
+        document: slow for a document of a million segments."""
+        q = np.zeros(len(queries), SEGS_QUERY_DTYPE)
+        for i, (doc, mode, min_seq) in enumerate(queries):
+            q[i] = (doc, mode, 0, SEGS_DOC_MIN_SEQ) if min_seq is None else (doc, mode, min_seq, 0)
+        h, segs, props, text = self.read_segment_lists_raw(q)
+        lists = []
+        for i in range(len(q)):
+            if h[i]["status"] != 0:
+                raise MergeTreeError(int(h[i]["status"]), f"read_segment_lists: document {int(q[i]['doc'])}")
+            so, to = int(h[i]["seg_offset"]), int(h[i]["text_offset"])
+            lists.append((segs[so: so + int(h[i]["n_segs"])], props[so: so + int(h[i]["n_segs"])],
+                          text[to: to + int(h[i]["n_text"])]))
+        if not info:
+            return lists
+        return lists, [{k: int(h[i][k]) for k in ("status", "cur_seq", "min_seq")} for i in range(len(q))]
 
     def _read_doc(self, doc, vptr):
         return self.lib.mte_read_doc(self.ctx, doc, vptr)

@@ -205,6 +205,9 @@ export class MergeTreeEngine {
    *  call until the next flush.  transient: also as Transient references;
    *  order: also the document-order keys. */
   prefetchRefs(clients?: BatchClient[] | null, options?: { transient?: boolean; order?: boolean }): void;
+  /** The blobs summarizeV1(chunkSize) / summarizeLegacy(undefined, chunkSize) return for each
+   *  client, from one device call (mte_read_segment_lists) for all of them. */
+  summarizeAll(clients: BatchClient[], options?: { format?: "v1" | "legacy"; chunkSize?: number }): Array<Record<string, any>>;
   digests(): BigUint64Array;
   statuses(): Int32Array;
   stats(): EngineStats;

@@ -483,6 +483,57 @@ class MergeTreeEngine {
     });
   }
 
+  /** Summaries of many documents at once (mte_read_segment_lists): one flush,
+   *  one sync and one device call give every client's segments already dropped
+   *  and coalesced at its document's minSeq, and the blobs are built from those
+   *  rows -- the blobs client.summarizeV1(chunkSize) (format "v1", the default)
+   *  or client.summarizeLegacy(undefined, chunkSize) (format "legacy") returns,
+   *  client by client; catch-up messages stay the caller's to add, as in
+   *  summarizeLegacy.  Throws for a document whose status is not OK.  One
+   *  wavefront walks each document: slow over a document of a million segments.
+   *  @param {BatchClient[]} clients
+   *  @param {{format?: "v1" | "legacy", chunkSize?: number}} [options] */
+  summarizeAll(clients, options) {
+    this.flush();
+    this.sync();
+    const o = options || {};
+    const format = o.format === undefined ? "v1" : o.format;
+    if (format !== "v1" && format !== "legacy") throw new MergeTreeError(-1, "summarizeAll: format " + format);
+    const n = clients.length, nk = this.nKeys;
+    const q = new Uint32Array(4 * n);
+    clients.forEach((c, i) => {
+      q.set([this._queryDoc("summarizeAll", i, { client: c }), format === "v1" ? 1 : 2, 0, 1], 4 * i);
+    });
+    if (n === 0) return [];
+    const r = this.addon.readSegmentLists(this.ctx, q, nk);
+    const dv = new DataView(r.segs.buffer, r.segs.byteOffset, r.segs.byteLength);
+    return clients.map((c, i) => {
+      const h = r.info.subarray(10 * i, 10 * i + 10);
+      if ((h[0] | 0) !== 0) throw new MergeTreeError(h[0] | 0, "summarizeAll: document " + q[4 * i]);
+      const curSeq = h[1] | 0, minSeq = h[2] | 0;
+      const s0 = h[6] + h[7] * 4294967296, t0 = h[8] + h[9] * 4294967296;
+      const segments = [];
+      for (let j = s0; j < s0 + h[3]; j++) {
+        const at = j * 32;
+        const textOff = t0 + dv.getUint32(at, true), len = dv.getUint32(at + 4, true);
+        const seq = dv.getInt32(at + 8, true), rseq = dv.getInt32(at + 12, true), kind = dv.getUint32(at + 24, true);
+        const raw = { json: segJson({ kind, props: this.interner.decode(nk ? r.props.subarray(j * nk, (j + 1) * nk) : []),
+          text: kind === 0 ? unitsToString(r.text.subarray(textOff, textOff + len)) : null }) };
+        if (seq > minSeq) { raw.seq = seq; raw.client = c.getLongClientId(dv.getInt32(at + 20, true)); }
+        if (rseq !== 0x7fffffff) {
+          const removers = dv.getUint32(at + 16, true), ids = [];
+          for (let k = 0; k < 32; k++) if ((removers >>> k) & 1) ids.push(c.getLongClientId(k));
+          raw.removedSeq = rseq;
+          raw.removedClient = ids[0];
+          raw.removedClientIds = ids;
+        }
+        segments.push(raw);
+      }
+      if (format === "v1") return v1Blobs(segments, minSeq, curSeq, o.chunkSize === undefined ? SNAPSHOT_V1_CHUNK_SIZE : o.chunkSize);
+      return legacyBlobs(segments.map((sp) => sp.json), minSeq, undefined, o.chunkSize === undefined ? SIZE_OF_FIRST_CHUNK : o.chunkSize);
+    });
+  }
+
   /** Per-doc canonical digests (4 x u64 each, DESIGN.md "Digest"). */
   digests() {
     this.flush();
@@ -1296,25 +1347,7 @@ class BatchClient {
   summarizeV1(chunkSize) {
     const size = chunkSize === undefined ? SNAPSHOT_V1_CHUNK_SIZE : chunkSize;
     const s = this.summarize();
-    const specs = s.segments.map((sp) => (Object.keys(sp).length === 1 ? sp.json : sp));
-    const lengths = s.segments.map((sp) => specLength(sp.json));
-    const md = { minSequenceNumber: s.minSeq, sequenceNumber: s.currentSeq, orderedChunkMetadata: [],
-      totalLength: 0, totalSegmentCount: 0 };
-    const chunks = [];
-    do { // getSeqLengthSegs (snapshotV1.ts:76-110)
-      const start = md.totalSegmentCount;
-      let n = 0, length = 0;
-      while (length < size && start + n < specs.length) { length += lengths[start + n]; n++; }
-      chunks.push({ version: "1", segmentCount: n, length, segments: specs.slice(start, start + n), startIndex: start });
-      md.totalSegmentCount += n;
-      md.totalLength += length;
-    } while (md.totalSegmentCount < specs.length);
-    const header = chunks.shift();
-    md.orderedChunkMetadata = [{ id: "header" }].concat(chunks.map((_, i) => ({ id: "body_" + i })));
-    header.headerMetadata = md;
-    const blobs = { header };
-    chunks.forEach((c, i) => { blobs["body_" + i] = c; });
-    return blobs;
+    return v1Blobs(s.segments, s.minSeq, s.currentSeq, size);
   }
 
   /**
@@ -1343,20 +1376,7 @@ class BatchClient {
       }
     }
     if (prev !== null) specs.push(segJson(prev));
-    const total = specs.reduce((a, sp) => a + specLength(sp), 0);
-    const header = legacyChunk(specs, size, 0, total, minSeq);
-    const ids = [{ id: "header" }];
-    if (header.chunkLengthChars < total) ids.push({ id: "body" });
-    header.headerMetadata = { orderedChunkMetadata: ids, sequenceNumber: minSeq, totalLength: total,
-      totalSegmentCount: specs.length };
-    const blobs = { header };
-    if (header.chunkSegmentCount < specs.length) {
-      blobs.body = legacyChunk(specs, total, header.chunkSegmentCount, total, minSeq);
-    }
-    const catchup = (catchUpMsgs || []).filter((m) => m.sequenceNumber > minSeq)
-      .map((m) => Object.assign({}, m, { minimumSequenceNumber: minSeq }));
-    if (catchup.length > 0) blobs.catchupOps = catchup;
-    return blobs;
+    return legacyBlobs(specs, minSeq, catchUpMsgs, size);
   }
 
   /** Segments the engine holds for this document (mte_read_segments), decoded. */
@@ -1397,6 +1417,45 @@ function sameProps(a, b) { // matchProperties (properties.ts:66-100) as the summ
 
 function canAppend(a, b) { // TextSegment.canAppend (textSegment.ts:72-77)
   return a.kind === 0 && b.kind === 0 && !a.text.endsWith("\n") && (a.text.length <= 256 || b.text.length <= 256);
+}
+
+function v1Blobs(segments, minSeq, currentSeq, size) { // SnapshotV1.emit (snapshotV1.ts:117-165)
+  const specs = segments.map((sp) => (Object.keys(sp).length === 1 ? sp.json : sp));
+  const lengths = segments.map((sp) => specLength(sp.json));
+  const md = { minSequenceNumber: minSeq, sequenceNumber: currentSeq, orderedChunkMetadata: [],
+    totalLength: 0, totalSegmentCount: 0 };
+  const chunks = [];
+  do { // getSeqLengthSegs (snapshotV1.ts:76-110)
+    const start = md.totalSegmentCount;
+    let n = 0, length = 0;
+    while (length < size && start + n < specs.length) { length += lengths[start + n]; n++; }
+    chunks.push({ version: "1", segmentCount: n, length, segments: specs.slice(start, start + n), startIndex: start });
+    md.totalSegmentCount += n;
+    md.totalLength += length;
+  } while (md.totalSegmentCount < specs.length);
+  const header = chunks.shift();
+  md.orderedChunkMetadata = [{ id: "header" }].concat(chunks.map((_, i) => ({ id: "body_" + i })));
+  header.headerMetadata = md;
+  const blobs = { header };
+  chunks.forEach((c, i) => { blobs["body_" + i] = c; });
+  return blobs;
+}
+
+function legacyBlobs(specs, minSeq, catchUpMsgs, size) { // SnapshotLegacy.emit (snapshotlegacy.ts:105-151)
+  const total = specs.reduce((a, sp) => a + specLength(sp), 0);
+  const header = legacyChunk(specs, size, 0, total, minSeq);
+  const ids = [{ id: "header" }];
+  if (header.chunkLengthChars < total) ids.push({ id: "body" });
+  header.headerMetadata = { orderedChunkMetadata: ids, sequenceNumber: minSeq, totalLength: total,
+    totalSegmentCount: specs.length };
+  const blobs = { header };
+  if (header.chunkSegmentCount < specs.length) {
+    blobs.body = legacyChunk(specs, total, header.chunkSegmentCount, total, minSeq);
+  }
+  const catchup = (catchUpMsgs || []).filter((m) => m.sequenceNumber > minSeq)
+    .map((m) => Object.assign({}, m, { minimumSequenceNumber: minSeq }));
+  if (catchup.length > 0) blobs.catchupOps = catchup;
+  return blobs;
 }
 
 function specLength(sp) {

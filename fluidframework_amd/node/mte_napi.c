@@ -57,6 +57,10 @@ typedef struct {
   uint32_t n_keys; /* the context's property planes: the read-outs size their buffers by it */
   uint16_t* text;  /* readTexts: where mte_read_texts fills, kept from call to call */
   uint64_t text_cap;
+  mte_seg* rows;   /* readSegmentLists: where mte_read_segment_lists fills, kept likewise */
+  uint32_t* rprops;
+  uint16_t* rtext;
+  uint64_t rows_cap, rtext_cap;
 } ctx_box;
 
 static void ctx_finalize(napi_env env, void* data, void* hint) {
@@ -65,6 +69,9 @@ static void ctx_finalize(napi_env env, void* data, void* hint) {
   ctx_box* b = (ctx_box*)data;
   if (b->ctx) mte_destroy(b->ctx);
   free(b->text);
+  free(b->rows);
+  free(b->rprops);
+  free(b->rtext);
   free(b);
 }
 
@@ -855,6 +862,82 @@ static napi_value js_read_ref_positions(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* readSegmentLists(ctx, queries, nKeys) -> {info Uint32Array(10n)
+   (mte_segs_info: status, curSeq, minSeq, nSegs, nText, 0, seg offset low,
+   high, text offset low, high), segs Uint8Array(32 rows) (mte_seg records),
+   props Uint32Array(rows * nKeys), text Uint16Array(n_text)}:
+   mte_read_segment_lists over queries = Uint32Array(4n) (mte_segs_query: doc,
+   mode, minSeq, flags), one call (a second only when the context's fill
+   buffers have to grow first).  Weak, as mte_find_tiles is. */
+extern __typeof__(mte_read_segment_lists) mte_read_segment_lists __attribute__((weak));
+
+static napi_value js_read_segment_lists(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return NULL;
+  ctx_box* box = get_box(env, argv[0]);
+  if (!box) return NULL;
+  void* q = NULL;
+  size_t qb = 0;
+  uint32_t nk = 0;
+  if (!get_bytes(env, argv[1], &q, &qb)) return NULL;
+  NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &nk));
+  if (!check_nkeys(env, box, nk)) return NULL;
+  if (!mte_read_segment_lists) {
+    throw_rc(env, MTE_E_UNSUPPORTED, NULL, "readSegmentLists: this engine library has no mte_read_segment_lists");
+    return NULL;
+  }
+  if (qb % sizeof(mte_segs_query) || qb / sizeof(mte_segs_query) > 0xffffffffu) {
+    throw_rc(env, MTE_E_INVALID_ARG, box->ctx, "readSegmentLists: buffer size");
+    return NULL;
+  }
+  const size_t n = qb / sizeof(mte_segs_query);
+  napi_value o, ab_i, ab_s, ab_p, ab_t, ti, ts, tp, tt;
+  void *pi = NULL, *ps = NULL, *pp = NULL, *pt = NULL;
+  uint64_t ns = 0, nt = 0;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(mte_segs_info), &pi, &ab_i));
+  for (int pass = 0; pass < 2; pass++) {
+    if (throw_rc(env, mte_read_segment_lists(box->ctx, (const mte_segs_query*)q, (uint32_t)n, (mte_segs_info*)pi,
+                                             box->rows, box->rprops, box->rows_cap, box->rtext, box->rtext_cap, &ns, &nt),
+                 box->ctx, "mte_read_segment_lists"))
+      return NULL;
+    if (ns <= box->rows_cap && nt <= box->rtext_cap) break;
+    if (pass == 1) { /* the documents cannot change between the two calls */
+      throw_rc(env, MTE_E_STATE, box->ctx, "readSegmentLists: the lists grew between the size and the fill");
+      return NULL;
+    }
+    free(box->rows), free(box->rprops), free(box->rtext);
+    box->rows_cap = box->rtext_cap = 0;
+    box->rows = (mte_seg*)malloc((size_t)(2 * ns + 1) * sizeof(mte_seg));
+    box->rprops = (uint32_t*)malloc((size_t)(2 * ns + 1) * (nk ? nk : 1) * 4);
+    box->rtext = (uint16_t*)malloc((size_t)(2 * nt + 1) * 2);
+    if (!box->rows || !box->rprops || !box->rtext) {
+      free(box->rows), free(box->rprops), free(box->rtext);
+      box->rows = NULL, box->rprops = NULL, box->rtext = NULL;
+      throw_rc(env, MTE_E_OOM, box->ctx, "readSegmentLists");
+      return NULL;
+    }
+    box->rows_cap = 2 * ns + 1;
+    box->rtext_cap = 2 * nt + 1;
+  }
+  const size_t npv = (size_t)ns * nk;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)ns * sizeof(mte_seg), &ps, &ab_s));
+  NAPI_CALL(env, napi_create_arraybuffer(env, npv * 4, &pp, &ab_p));
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)nt * 2, &pt, &ab_t));
+  if (ns) memcpy(ps, box->rows, (size_t)ns * sizeof(mte_seg));
+  if (npv) memcpy(pp, box->rprops, npv * 4);
+  if (nt) memcpy(pt, box->rtext, (size_t)nt * 2);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n * 10, ab_i, 0, &ti));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, (size_t)ns * sizeof(mte_seg), ab_s, 0, &ts));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, npv, ab_p, 0, &tp));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint16_array, (size_t)nt, ab_t, 0, &tt));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "info", ti);
+  napi_set_named_property(env, o, "segs", ts);
+  napi_set_named_property(env, o, "props", tp);
+  napi_set_named_property(env, o, "text", tt);
+  return o;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   const napi_property_descriptor d[] = {
       {"abiVersion", NULL, js_abi_version, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -891,6 +974,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"readTexts", NULL, js_read_texts, NULL, NULL, NULL, napi_default, NULL},
       {"propsAt", NULL, js_props_at, NULL, NULL, NULL, napi_default, NULL},
       {"readRefPositions", NULL, js_read_ref_positions, NULL, NULL, NULL, napi_default, NULL},
+      {"readSegmentLists", NULL, js_read_segment_lists, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

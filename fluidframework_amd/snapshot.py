@@ -1,5 +1,9 @@
 """Summary bodies over the engine's segments.
 
+write_bodies(), write_v1_all() and write_legacy_all() do the same for many
+documents from one read (EngineBase.read_segment_lists: the engine drops and
+coalesces; reduce_segments() states its two rules over a raw list).
+
 write_body() is the summary writer: SnapshotV1.extractSegment
 (packages/dds/merge-tree/src/snapshotV1.ts:189-265) over the segments a
 document holds (mte_read_segments), for an observer (no unacked segments):
@@ -34,7 +38,8 @@ import json
 
 import numpy as np
 
-from .abi import DOC_INIT_DTYPE, MTE_VALUE_UNEQUAL, NOT_REMOVED, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE
+from .abi import (DOC_INIT_DTYPE, MTE_VALUE_UNEQUAL, NO_PROPS, NOT_REMOVED, PROP_DTYPE, PROPSET_DTYPE, SEG_DTYPE, SEGS_LEGACY,
+                  SEGS_RAW, SEGS_V1)
 from .packing import units_to_str, utf16_units
 
 TEXT_SEGMENT_GRANULARITY = 256  # textSegment.ts (TextSegmentGranularity)
@@ -145,6 +150,96 @@ def load_bodies(bodies, windows, flags, n_keys):
             np.array(offs, np.uint64), np.array(rows, SEG_DTYPE) if rows else np.zeros(0, SEG_DTYPE))
 
 
+def soft_joins_break(lens, soft):
+    """The length condition of TextSegment.canAppend in closed form: segment i of a
+    soft run (a chain joined by every other condition; soft[i]: i joins i - 1) starts a
+    new output segment exactly when len(i) > 256 and the kept units from the run's head
+    h up to i exceed 256 -- h is not moved by such a break -> bool[n]."""
+    lens = np.asarray(lens, np.int64)
+    soft = np.asarray(soft, bool)
+    before = np.concatenate([[0], np.cumsum(lens)[:-1]]) if len(lens) else np.zeros(0, np.int64)
+    head = np.maximum.accumulate(np.where(soft, 0, np.arange(len(lens))))
+    return soft & (lens > TEXT_SEGMENT_GRANULARITY) & (before - before[head] > TEXT_SEGMENT_GRANULARITY)
+
+
+def reduce_segments(segs, props, text, mode, min_seq):
+    """mte_read_segment_lists' MTE_SEGS_V1 / MTE_SEGS_LEGACY over a raw list (what
+    read_segments returns) at minSeq -> (rows, props, text) as the call returns them:
+    the rows load_bodies builds from write_body (V1) or extract_legacy (legacy),
+    with propset MTE_NO_PROPS and text_off into the returned text."""
+    if mode == SEGS_RAW:
+        return segs.copy(), props.copy(), text.copy()
+    seq, rs = segs["seq"], segs["removed_seq"]
+    removed = rs != NOT_REMOVED
+    if mode == SEGS_V1:
+        keep, elig = ~(removed & (rs <= min_seq)), ~removed & (seq <= min_seq)
+    else:
+        keep = (seq <= min_seq) & (rs > min_seq)
+        elig = keep
+    idx = np.flatnonzero(keep)
+    k, kp, e = segs[idx], props[idx], elig[idx]
+    n = len(idx)
+    lens = k["len"].astype(np.int64)
+    is_text = k["kind"] == 0
+    last = np.zeros(n, np.uint16)
+    has = is_text & (lens > 0)
+    last[has] = text[(k["text_off"].astype(np.int64) + lens - 1)[has]]
+    soft = np.zeros(n, bool)
+    if n > 1:
+        soft[1:] = (e[1:] & e[:-1] & is_text[1:] & is_text[:-1] & (last[:-1] != NEWLINE)
+                    & (kp[1:] == kp[:-1]).all(axis=1) & ~((kp[1:] & MTE_VALUE_UNEQUAL) != 0).any(axis=1))
+    start = ~soft | soft_joins_break(lens, soft)
+    first = np.flatnonzero(start)
+    rows = k[first].copy()
+    ends = np.concatenate([np.cumsum(lens)[first[1:] - 1], [lens.sum()]]) if len(first) else np.zeros(0, np.int64)
+    rows["len"] = ends - (np.cumsum(lens) - lens)[first]
+    re = e[first]
+    drop = re | (rows["seq"] <= min_seq)  # seq and client go
+    rows["seq"][drop], rows["client"][drop] = 0, -1
+    rows["removed_seq"][re], rows["removers"][re] = NOT_REMOVED, 0
+    rows["propset"] = NO_PROPS
+    tlen = np.where(is_text, lens, 0)
+    rows["text_off"] = np.where(rows["kind"] == 0, (np.cumsum(tlen) - tlen)[first], 0)
+    parts = [text[int(o): int(o) + int(ln)] for o, ln, t in zip(k["text_off"], lens, is_text) if t]
+    return rows, kp[first].copy(), np.concatenate(parts) if parts else np.zeros(0, np.uint16)
+
+
+def _row_spec(s, props, text, min_seq, first_remover=None):
+    """One row of a MTE_SEGS_V1 list -> the spec write_body gives."""
+    cur = {"kind": int(s["kind"]), "props": tuple(int(x) for x in props),
+           "text": text[int(s["text_off"]): int(s["text_off"]) + int(s["len"])].tolist() if int(s["kind"]) == 0 else None}
+    raw = {"json": _json(cur)}
+    if int(s["seq"]) > min_seq:
+        raw["seq"] = int(s["seq"])
+        raw["client"] = int(s["client"])
+    if int(s["removed_seq"]) != NOT_REMOVED:
+        raw["removedSeq"] = int(s["removed_seq"])
+        ids = [c for c in range(32) if (int(s["removers"]) >> c) & 1]
+        first = first_remover(raw["removedSeq"]) if first_remover else None
+        if first in ids:
+            ids.remove(first)
+            ids.insert(0, first)
+        raw["removedClient"] = ids[0]
+        raw["removedClientIds"] = ids
+    return raw
+
+
+def _read_reduced(engine, docs, min_seqs, mode):
+    lists, infos = engine.read_segment_lists(
+        [(d, mode, None if min_seqs is None else min_seqs[i]) for i, d in enumerate(docs)], info=True)
+    ms = [int(h["min_seq"]) if min_seqs is None else int(min_seqs[i]) for i, h in enumerate(infos)]
+    return lists, infos, ms
+
+
+def write_bodies(engine, docs, min_seqs=None, first_remover=None):
+    """write_body for every document of `docs` from one read (read_segment_lists,
+    MTE_SEGS_V1): min_seqs[i] for docs[i], or each document's own minSeq;
+    first_remover maps a document to write_body's callable (or None) -> [body]."""
+    lists, _, ms = _read_reduced(engine, docs, min_seqs, SEGS_V1)
+    fr = first_remover or {}
+    return [[_row_spec(segs[j], props[j], text, ms[i], fr.get(d) if hasattr(fr, "get") else fr[d])
+             for j in range(len(segs))] for i, (d, (segs, props, text)) in enumerate(zip(docs, lists))]
+
 # --- V1 format (newMergeTreeSnapshotFormat: true) ----------------------------------------------
 
 CHUNK_SIZE_V1 = 10000  # SnapshotV1.chunkSize, snapshotV1.ts:43
@@ -170,7 +265,10 @@ def write_v1(engine, doc, min_seq, cur_seq, chunk_size=CHUNK_SIZE_V1, first_remo
     "header" carries headerMetadata {minSequenceNumber, sequenceNumber, orderedChunkMetadata,
     totalLength, totalSegmentCount}; "body_0", "body_1", ... the rest, ~chunk_size units each.
     Segments below the MSN are plain specs, the others IJSONSegmentWithMergeInfo."""
-    body = write_body(engine, doc, min_seq, first_remover)
+    return _v1_blobs(write_body(engine, doc, min_seq, first_remover), min_seq, cur_seq, chunk_size)
+
+
+def _v1_blobs(body, min_seq, cur_seq, chunk_size):
     specs = [sp if len(sp) > 1 else sp["json"] for sp in body]
     lengths = [_seg_length(sp["json"]) for sp in body]
     md = {"minSequenceNumber": min_seq, "sequenceNumber": cur_seq, "orderedChunkMetadata": [],
@@ -189,6 +287,19 @@ def write_v1(engine, doc, min_seq, cur_seq, chunk_size=CHUNK_SIZE_V1, first_remo
     blobs = {"header": head}
     blobs.update({f"body_{i}": c for i, c in enumerate(chunks)})
     return blobs
+
+
+def write_v1_all(engine, docs, min_seqs=None, cur_seqs=None, chunk_size=CHUNK_SIZE_V1, first_remover=None):
+    """write_v1 for every document of `docs` from one read: min_seqs / cur_seqs default
+    to each document's own window -> [{blob name: chunk}]."""
+    lists, infos, ms = _read_reduced(engine, docs, min_seqs, SEGS_V1)
+    fr = first_remover or {}
+    out = []
+    for i, (d, (segs, props, text)) in enumerate(zip(docs, lists)):
+        f = fr.get(d) if hasattr(fr, "get") else fr[d]
+        body = [_row_spec(segs[j], props[j], text, ms[i], f) for j in range(len(segs))]
+        out.append(_v1_blobs(body, ms[i], int(infos[i]["cur_seq"]) if cur_seqs is None else int(cur_seqs[i]), chunk_size))
+    return out
 
 
 def to_latest(path, chunk):
@@ -354,7 +465,10 @@ def write_legacy(engine, doc, min_seq, catchup=None, chunk_size=SIZE_OF_FIRST_CH
     snapshotChunks.ts:168-186; minSequenceNumber is absent, so the loader takes
     sequenceNumber = minSeq for both ends of the window), "body" the rest when any, and
     "catchupOps" the caller's messages above minSeq when given."""
-    specs = extract_legacy(engine, doc, min_seq)
+    return _legacy_blobs(extract_legacy(engine, doc, min_seq), min_seq, catchup, chunk_size)
+
+
+def _legacy_blobs(specs, min_seq, catchup, chunk_size):
     total = sum(_seg_length(s) for s in specs)
     c1 = _legacy_chunk(specs, chunk_size, 0, total, min_seq)
     ids = [{"id": "header"}] + ([{"id": "body"}] if c1["chunkLengthChars"] < total else [])
@@ -368,6 +482,18 @@ def write_legacy(engine, doc, min_seq, catchup=None, chunk_size=SIZE_OF_FIRST_CH
     if catchup is not None and len(catchup) > 0:
         blobs["catchupOps"] = catchup
     return blobs
+
+
+def write_legacy_all(engine, docs, min_seqs=None, catchups=None, chunk_size=SIZE_OF_FIRST_CHUNK):
+    """write_legacy for every document of `docs` from one read (MTE_SEGS_LEGACY):
+    min_seqs default to each document's own minSeq; catchups[i] are the caller's
+    messages for docs[i] -> [{blob name: chunk}]."""
+    lists, _, ms = _read_reduced(engine, docs, min_seqs, SEGS_LEGACY)
+    out = []
+    for i, (segs, props, text) in enumerate(lists):
+        specs = [_row_spec(segs[j], props[j], text, ms[i])["json"] for j in range(len(segs))]
+        out.append(_legacy_blobs(specs, ms[i], None if catchups is None else catchups[i], chunk_size))
+    return out
 
 
 def legacy_window(blobs):

@@ -768,6 +768,70 @@ typedef struct mte_ref_info  { int32_t status, cur_seq, min_seq; uint32_t length
 int mte_read_ref_positions(mte_ctx* ctx, const mte_ref_query* q, uint32_t n, mte_ref_info* info,
                            int32_t* pos, int64_t* order, uint64_t cap);
 
+/* ---- Batched summary read-out: segment lists for many documents ------------
+ * mte_read_segments for any number of documents in one device call, as it is
+ * (MTE_SEGS_RAW) or already reduced the way a summary writer reduces it at a
+ * minSeq m (MTE_SEGS_V1: SnapshotV1.extractSegment, snapshotV1.ts:189-265;
+ * MTE_SEGS_LEGACY: SnapshotLegacy.extractSync, snapshotlegacy.ts:153-211).
+ * m is the query's min_seq, or the document's own with MTE_SEGS_DOC_MIN_SEQ.
+ *
+ * MTE_SEGS_RAW: the rows, property rows and text of mte_read_segments, field
+ * for field; text_off is relative to the query's own text (info.text_offset)
+ * and 0 for a marker, propset is MTE_NO_PROPS.
+ *
+ * The other two modes are functions of that list and m.
+ *   V1: a segment with removed_seq <= m vanishes (it does not end a run).  A
+ *     segment not removed with seq <= m is eligible: it loses its merge info
+ *     (seq 0, client -1, removed_seq MTE_NOT_REMOVED, removers 0) and joins the
+ *     previous kept segment when that is eligible too and the conditions below
+ *     hold.  Any other segment stands alone with removed_seq / removers kept,
+ *     and seq / client kept when seq > m (0 / -1 otherwise).
+ *   Legacy: a segment is kept when seq <= m and removed_seq > m; every kept
+ *     segment is eligible (its removal above m is dropped too).
+ *   Kept segment i joins kept segment i-1 when both are eligible text, the last
+ *   unit of i-1 is not 0x000A, their property rows are equal over all n_keys,
+ *   no value of i has MTE_VALUE_UNEQUAL, and len(run so far) <= 256 or
+ *   len(i) <= 256 (TextSegment.canAppend, textSegment.ts:72-77).  A row's len
+ *   and text are its run's; its property row is its first segment's.
+ *
+ * info[i] holds the document's status and collab window, the rows and text
+ * units the query gives (n_text counts the units of text rows only) and where
+ * they start in segs / props ([row][n_keys]) and text: the exclusive prefix
+ * sums of the counts in query order.  Queries may name documents in any
+ * order, with repeats; n == 0 launches nothing.  A document whose status is
+ * not MTE_OK answers that status with counts 0 (mte_read_segments still
+ * serves it); one that holds a removed segment with a remover of short id
+ * >= 32 answers MTE_E_UNSUPPORTED with counts 0, as mte_read_segments refuses
+ * it; the other queries of the call are answered.
+ *
+ * Size-then-fill: info and the totals are always produced; segs, props and
+ * text are written only when all are given (props may be NULL without keys)
+ * and *n_segs_total <= seg_cap and *n_text_total <= text_cap, and left
+ * untouched otherwise (the call still returns MTE_OK).  The device work is one
+ * upload of the queries, a count kernel, one download of info and, when
+ * filling, an upload of the offsets, a gather kernel and one download of the
+ * rows, property rows and units: two synchronisations, whatever n.  Text is
+ * read from the device's arena.  MTE_E_INVALID_ARG, before any launch, for a
+ * null context or totals, doc >= n_docs, an unknown mode or flag or a negative
+ * min_seq without MTE_SEGS_DOC_MIN_SEQ.  One wavefront walks a whole document
+ * per query (no tile-parallel variant exists yet).                           */
+#define MTE_SEGS_RAW 0u
+#define MTE_SEGS_V1 1u
+#define MTE_SEGS_LEGACY 2u
+#define MTE_SEGS_DOC_MIN_SEQ 0x1u          /* m = the document's own minSeq */
+typedef struct mte_segs_query { uint32_t doc, mode; int32_t min_seq; uint32_t flags; } mte_segs_query;  /* 16 B */
+typedef struct mte_segs_info {
+  int32_t  status, cur_seq, min_seq;
+  uint32_t n_segs;      /* rows this query gives */
+  uint32_t n_text;      /* text units this query gives */
+  uint32_t reserved;
+  uint64_t seg_offset;  /* where its rows start in segs (and props) */
+  uint64_t text_offset; /* where its units start in text */
+} mte_segs_info;        /* 40 B */
+int mte_read_segment_lists(mte_ctx* ctx, const mte_segs_query* q, uint32_t n, mte_segs_info* info,
+                           mte_seg* segs, uint32_t* props, uint64_t seg_cap, uint16_t* text, uint64_t text_cap,
+                           uint64_t* n_segs_total, uint64_t* n_text_total);
+
 int mte_doc_status(mte_ctx* ctx, int32_t* out, uint32_t n_docs);
 int mte_stats_get(mte_ctx* ctx, mte_stats* out);
 /* Statistics accounting (the counters of mte_stats, like the reference's
